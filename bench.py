@@ -11,7 +11,10 @@ grid is replicated.
 
 Launch: `python bench.py --gpus 1 --steps K --warmup W`, or for N>1
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline; `--full` adds, after
+the timed steps, everything else the line can carry: the roofline of the hot build (a profiled pass of K steps of its own),
+the store-on figure, BASELINE configs 3 and 4, and the CPU baseline (run before the GPU is touched).  `--dump-outputs DIR`
+writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -31,6 +34,7 @@ HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6           # MI355X vector fp64 peak
 N_SIMD, SIMD_CLOCK_HZ = 1024, 2.4e9   # 256 CUs x 4 SIMDs; one wave-instruction (64 lanes, fp64 included) issues per 4 cycles per SIMD
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "r03_pmc_summary.json")   # rocprofv3 --pmc passes of this same command (tools/profiling/run_pmc.sh)
+DUMP_BERGS, DUMP_SEED = 1 << 16, 20240   # --dump-outputs: the fixed sample of bergs (59 float64 columns of 64 Ki rows: 31 MB)
 
 
 def _cpu_worker(nbergs, nsteps, seed):
@@ -171,6 +175,89 @@ def other_configs(np, torch, S, T, Icebergs, budget_s=75.0):
     return out
 
 
+def dump_outputs(out_dir, np, T, ib, ids0):
+    """--dump-outputs: what the timed path handed its caller after its last step, one float64 DIR/<name>.npy per array: the
+    gathered per-cell fields (out_*), the per-cell fluxes to the ocean (acc_*, the planes before the 9-slot footprints), the
+    step's scalars, and every member of a fixed, seeded sample of bergs picked by id (berg_*, rows in the order of berg_id).
+    A sampled berg that is no longer in the population (melted, or dropped by the re-binning) has every member 0, berg_alive
+    included, so that every output is finite.  Rows are matched by id because the re-binning reorders the population."""
+    os.makedirs(out_dir, exist_ok=True)
+    acc, out, scal = ib.fetch()
+    arrays = {"scalars": scal}
+    for name, k in T.OUT_NAMES.items():
+        arrays["out_" + name] = out[k]
+    for key, k in T.ENUMS.items():
+        if key.startswith("KID_A_") and k < T.ENUMS["KID_A_MASS_ON_OCEAN"]:
+            arrays["acc_" + key[len("KID_A_"):].lower()] = acc[k]
+    ids = np.sort(np.random.default_rng(DUMP_SEED).choice(ids0, size=min(DUMP_BERGS, len(ids0)), replace=False))
+    b = ib.download_bergs()
+    live = np.flatnonzero(b["alive"] != 0)
+    order = live[np.argsort(b["id"][live], kind="stable")]
+    pos = np.searchsorted(b["id"][order], ids)
+    hit = pos < len(order)
+    hit[hit] = b["id"][order[pos[hit]]] == ids[hit]
+    rows = order[pos[hit]]
+    arrays["berg_id"] = ids
+    for name in T.BERG_F64_NAMES + T.BERG_I32_NAMES:
+        col = np.zeros(len(ids))
+        col[hit] = b[name][rows]
+        arrays["berg_" + name] = col
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def roofline(ib, nbergs, steps, berg_ms, launches):
+    """The hot build of berg_kernel against its two bounds, from the HIP-event pairs of a profiled pass of `steps` steps."""
+    # the dominant kernel is the hot build of berg_kernel: one launch per step, or two (one per half-population)
+    # when the pipelined schedule is on; every berg goes through exactly one of them per step
+    kern_ms = berg_ms / max(launches, 1)
+    bergs_per_launch = nbergs * steps / max(launches, 1)
+    achieved = ALGO_BYTES_PER_BERG_STEP * bergs_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    # HBM bytes and VALU instructions per launch of the dominant kernel: PMC counters cannot be read from inside the
+    # process, so these come from the committed rocprofv3 --pmc passes of this same command (profiles/r02_pmc_summary.json,
+    # tools/profiling/run_pmc.sh) and are reported only for the population those passes were taken at
+    traffic, traffic_src, valu_per_berg_step, pmc, pmc_note = None, None, None, None, None
+    try:
+        with open(PMC_SUMMARY) as f:
+            summary = json.load(f)
+        pmc = summary["hot"]
+        libv = ib.lib.kid_version().decode()
+        if not summary.get("complete", False):
+            pmc_note = "counter passes incomplete in " + os.path.basename(PMC_SUMMARY)
+        elif summary.get("library") != libv:
+            pmc_note = "counters were taken on another build (%s), this run is %s" % (summary.get("library"), libv)
+        elif abs(pmc["grid_size_mean"] - bergs_per_launch) > 256:
+            pmc_note = "counters were taken at another population"
+        else:
+            traffic = pmc["hbm"]["traffic_bytes_per_launch"]
+            traffic_src = "profiles/%s (rocprofv3 --pmc FETCH_SIZE, WRITE_SIZE in separate passes; gfx950 fetch correction x2)" % os.path.basename(PMC_SUMMARY)
+            valu_per_berg_step = pmc["valu_wave_instr_per_berg_step"]
+    except (OSError, KeyError, ValueError) as e:
+        pmc_note = "no PMC summary (%r)" % (e,)
+    hbm_frac = achieved / HBM_PEAK_GBS
+    # the other bound: one wave-instruction (fp64 included) per 4 cycles per SIMD.  instructions per berg-step x waves / time
+    valu = None
+    if valu_per_berg_step and kern_ms > 0:
+        issue_s = valu_per_berg_step * (bergs_per_launch / 64.0) * 4.0 / (N_SIMD * SIMD_CLOCK_HZ)
+        valu = {"wave_instr_per_berg_step": valu_per_berg_step, "floor_ms": 1e3 * issue_s, "frac": issue_s / (kern_ms * 1e-3),
+                "peak": "1 wave-instruction / 4 cycles / SIMD, %d SIMDs at %.1f GHz" % (N_SIMD, SIMD_CLOCK_HZ / 1e9),
+                "source": "SQ_INSTS_VALU per launch / waves (profiles/%s)" % os.path.basename(PMC_SUMMARY)}
+        clk = pmc.get("shader_clock_ghz")   # GRBM_GUI_ACTIVE / 8 XCDs / the launch's duration in the same PMC pass
+        if clk:
+            valu["shader_clock_ghz_measured"] = clk
+            valu["frac_at_measured_clock"] = valu["frac"] * (SIMD_CLOCK_HZ / 1e9) / clk
+    binding = "valu_fp64_issue" if (valu and valu["frac"] > hbm_frac) else "hbm"
+    # `bound` = the bound that binds the dominant kernel.  achieved / peak / frac are the HBM figures (algorithmic bytes over
+    # the kernel's launch time, the quantity BASELINE.json's target is stated in); `valu_fp64_issue` carries the other one.
+    return {"bound": binding, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_frac,
+            "frac_of": "hbm", "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_frac},
+            "valu_fp64_issue": valu,
+            "traffic": traffic, "traffic_source": traffic_src, "traffic_note": pmc_note,
+            "kernel": "berg_kernel<true, true, 14u, true, 1> (RK4, old interp order, evolve|thermo|spread, hot build, plain namelist)",
+            "kernel_ms_avg": kern_ms, "kernel_launches": launches, "bergs_per_launch": bergs_per_launch,
+            "algorithmic_bytes_per_berg_step": ALGO_BYTES_PER_BERG_STEP, "profiled_steps": steps}
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-worker":
         return _cpu_worker(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
@@ -181,7 +268,6 @@ def main():
     ap.add_argument("--spinup", type=int, default=24, help="untimed steps before the warm-up: the synthetic bergs start at rest and take ~20 steps "
                     "to reach their drift (per-launch time of the hot build over those steps at 1e7 bergs: 0.81, 0.89, 0.98, 1.06, 1.02, 0.96 ... 0.88, then 0.82 flat); 0 = start timing in the transient")
     ap.add_argument("--bergs", type=int, default=10_000_000, help="bergs per GPU (BASELINE target: >= 1e7 bergs stepped; configs[4]: 1e7 per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="N>1: keep the all-reduce and the gather on the critical path")
     ap.add_argument("--split-general", action="store_true", help="experiment: hot build in two halves, general build on the side stream")
     ap.add_argument("--force-collective", action="store_true", help="rehearsal: run the N>1 code path (RCCL all-reduce) with one rank")
@@ -191,7 +277,11 @@ def main():
     ap.add_argument("--slow-lane", action="store_true", help="step the bergs the hot build hands over on a second stream for two steps (round 2's default: it paid while the "
                     "hot build left room for other kernels on a SIMD; with three waves of 160 registers it does not: 1.09 against 1.05 ms/step at 1e7 bergs)")
     ap.add_argument("--no-slow-lane", action="store_true", help="(default since round 3) keep the general build between two hot builds")
-    ap.add_argument("--no-other-configs", action="store_true", help="headline only: skip the informational runs after the timed region (store-on figure, configs 3 and 4)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the line can carry: the roofline (a profiled pass of "
+                    "--steps steps of its own), the store-on figure, configs 3 and 4, and the CPU baseline (before the GPU is touched)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the informational runs after the timed region (store-on figure, configs 3 and 4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64; dump_outputs)")
     ap.add_argument("--cpu-bergs", type=int, default=500_000)
     ap.add_argument("--cpu-steps", type=int, default=8)
     args = ap.parse_args()
@@ -199,7 +289,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     # CPU baseline first, in GPU-free child processes, before this process touches the GPU (rank 0 at N=1 only)
-    cpu_line = cpu_baseline(args.cpu_bergs, args.cpu_steps) if (world == 1 and rank == 0 and not args.no_cpu_baseline) else None
+    cpu_line = cpu_baseline(args.cpu_bergs, args.cpu_steps) if (args.full and world == 1 and rank == 0 and not args.no_cpu_baseline) else None
 
     import numpy as np
     import torch
@@ -275,64 +365,33 @@ def main():
     for _ in range(args.spinup + args.warmup):
         step()
     fence()
-    ib.profile(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     t_submit = time.perf_counter() - t0   # host time to enqueue the steps (diagnostic: is the host the bottleneck?)
     fence()
     elapsed = time.perf_counter() - t0
-    berg_ms, launches, _ = ib.profile_get()
-    ib.profile(False)
     elapsed_min = elapsed
     if dist is not None:
         tt = torch.tensor([elapsed, -elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, elapsed_min = float(tt[0].item()), -float(tt[1].item())
     n_slots, n_alive = ib.num_bergs()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, T, ib, bergs["id"])
+
+    if args.full:
+        # the roofline: HIP events around every hot-build launch of a pass of its own, so that the timed steps carry none
+        ib.profile(True)
+        for _ in range(args.steps):
+            step()
+        fence()
+        berg_ms, launches, _ = ib.profile_get()
+        ib.profile(False)
 
     if rank == 0:
         total_bergs = args.bergs * world
         value = total_bergs * args.steps / elapsed
-        # the dominant kernel is the hot build of berg_kernel: one launch per step, or two (one per half-population)
-        # when the pipelined schedule is on; every berg goes through exactly one of them per step
-        kern_ms = berg_ms / max(launches, 1)
-        bergs_per_launch = args.bergs * args.steps / max(launches, 1)
-        achieved = ALGO_BYTES_PER_BERG_STEP * bergs_per_launch / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-        # HBM bytes and VALU instructions per launch of the dominant kernel: PMC counters cannot be read from inside the
-        # process, so these come from the committed rocprofv3 --pmc passes of this same command (profiles/r02_pmc_summary.json,
-        # tools/profiling/run_pmc.sh) and are reported only for the population those passes were taken at
-        traffic, traffic_src, valu_per_berg_step, pmc, pmc_note = None, None, None, None, None
-        try:
-            with open(PMC_SUMMARY) as f:
-                summary = json.load(f)
-            pmc = summary["hot"]
-            libv = ib.lib.kid_version().decode()
-            if not summary.get("complete", False):
-                pmc_note = "counter passes incomplete in " + os.path.basename(PMC_SUMMARY)
-            elif summary.get("library") != libv:
-                pmc_note = "counters were taken on another build (%s), this run is %s" % (summary.get("library"), libv)
-            elif abs(pmc["grid_size_mean"] - bergs_per_launch) > 256:
-                pmc_note = "counters were taken at another population"
-            else:
-                traffic = pmc["hbm"]["traffic_bytes_per_launch"]
-                traffic_src = "profiles/%s (rocprofv3 --pmc FETCH_SIZE, WRITE_SIZE in separate passes; gfx950 fetch correction x2)" % os.path.basename(PMC_SUMMARY)
-                valu_per_berg_step = pmc["valu_wave_instr_per_berg_step"]
-        except (OSError, KeyError, ValueError) as e:
-            pmc_note = "no PMC summary (%r)" % (e,)
-        hbm_frac = achieved / HBM_PEAK_GBS
-        # the other bound: one wave-instruction (fp64 included) per 4 cycles per SIMD.  instructions per berg-step x waves / time
-        valu = None
-        if valu_per_berg_step and kern_ms > 0:
-            issue_s = valu_per_berg_step * (bergs_per_launch / 64.0) * 4.0 / (N_SIMD * SIMD_CLOCK_HZ)
-            valu = {"wave_instr_per_berg_step": valu_per_berg_step, "floor_ms": 1e3 * issue_s, "frac": issue_s / (kern_ms * 1e-3),
-                    "peak": "1 wave-instruction / 4 cycles / SIMD, %d SIMDs at %.1f GHz" % (N_SIMD, SIMD_CLOCK_HZ / 1e9),
-                    "source": "SQ_INSTS_VALU per launch / waves (profiles/%s)" % os.path.basename(PMC_SUMMARY)}
-            clk = pmc.get("shader_clock_ghz")   # GRBM_GUI_ACTIVE / 8 XCDs / the launch's duration in the same PMC pass
-            if clk:
-                valu["shader_clock_ghz_measured"] = clk
-                valu["frac_at_measured_clock"] = valu["frac"] * (SIMD_CLOCK_HZ / 1e9) / clk
-        binding = "valu_fp64_issue" if (valu and valu["frac"] > hbm_frac) else "hbm"
         line = {
             "metric": "berg_steps_per_sec", "value": value, "unit": "berg-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "spinup_steps": args.spinup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -346,16 +405,9 @@ def main():
             "library": ib.lib.kid_version().decode(),   # names the build switches (an experiment or exact-math build says so)
             "per_gpu_value": value / world, "host_submit_ms_per_step": 1e3 * t_submit / args.steps,
             "ms_per_step_rank_max": 1e3 * elapsed / args.steps, "ms_per_step_rank_min": 1e3 * elapsed_min / args.steps,
-            # `bound` = the bound that binds the dominant kernel.  achieved / peak / frac are the HBM figures (algorithmic bytes over
-            # the kernel's launch time, the quantity BASELINE.json's target is stated in); `valu_fp64_issue` carries the other one.
-            "roofline": {"bound": binding, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_frac,
-                         "frac_of": "hbm", "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_frac},
-                         "valu_fp64_issue": valu,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_note": pmc_note,
-                         "kernel": "berg_kernel<true, true, 14u, true, 1> (RK4, old interp order, evolve|thermo|spread, hot build, plain namelist)",
-                         "kernel_ms_avg": kern_ms, "kernel_launches": launches, "bergs_per_launch": bergs_per_launch,
-                         "algorithmic_bytes_per_berg_step": ALGO_BYTES_PER_BERG_STEP},
         }
+    if rank == 0 and args.full:
+        line["roofline"] = roofline(ib, args.bergs, args.steps, berg_ms, launches)
         # The headline runs the way config 2 is configured (ignore_traj=T: berg%uo..hi are not stored back, IB:2890-2894 has no
         # reader).  A host that samples trajectories, prints bergs_chksum or migrates bergs needs those 11 members: the same
         # population with the store on (the plain hot build again, K = 3: the eleven members written right after the
@@ -390,6 +442,7 @@ def main():
             ib.close()   # (3.9 GB of berg state + the re-binning buffers: config 3 needs the room to be quick to allocate)
             torch.cuda.set_stream(torch.cuda.default_stream(dev))
             line["other_configs"] = other_configs(np, torch, S, T, Icebergs)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -90,23 +90,14 @@ def test_fortran_module_covers_the_header():
 
 def test_icebergs_nml_table_matches_the_reference_namelist():
     """tools/icebergs_nml_table.py (the declarations the Fortran glue reads &icebergs_nml with) lists exactly the variables of the
-    reference's namelist statement, in its order (icebergs_framework.F90:823-856).  Runs where the reference tree is present (the
-    build container); a Fortran namelist read fails on any name the group does not declare, so a missing one would break a
-    maintainer's input.nml."""
+    reference's namelist statement, in its order (icebergs_framework.F90:825-856, recorded in tests/golden/icebergs_nml_names.json);
+    a Fortran namelist read fails on any name the group does not declare, so a missing one would break a maintainer's input.nml."""
+    import json
     import os
     import re
     import sys
-    ref = "/root/reference/src/icebergs_framework.F90"
-    if not os.path.exists(ref):
-        import pytest
-        pytest.skip("reference tree not present")
-    src = open(ref).read()
-    m = re.search(r"namelist\s*/icebergs_nml/(.*?)\n\s*\n", src, re.S | re.I)
-    assert m, "namelist statement not found"
-    body = re.sub(r"!.*", "", m.group(1))
-    body = body.replace("&", " ")
-    names = [x.strip() for x in body.replace("\n", " ").split(",") if x.strip()]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = json.load(open(os.path.join(root, "tests", "golden", "icebergs_nml_names.json")))["names"]
     sys.path.insert(0, os.path.join(root, "tools"))
     from icebergs_nml_table import ICEBERGS_NML
     mine = [r[0] for r in ICEBERGS_NML]
