@@ -654,6 +654,81 @@ __device__ __forceinline__ double groundfrac_of(const kid_params &p, double od, 
   return gf;
 }
 
+// Pieces of a sub-step shared by the per-launch kernels and the fused loop (mts_substeps_kernel)
+struct LonLat { double lon, lat; };
+struct UV { double u, v; };
+struct Element { double M, R, A; };   // mass, radius, area: under constant_interaction_LW those of the constant element
+__device__ __forceinline__ Element element_of(const kid_params &p, const BergPtrs &b, long long k) {
+  if (p.constant_interaction_LW) {
+    const double A = p.constant_length * p.constant_width;
+    return Element{A * MF(KID_B_THICKNESS, k) * p.rho_bergs, radius_of(p, A), A};
+  }
+  const double A = MF(KID_B_LENGTH, k) * MF(KID_B_WIDTH, k);
+  return Element{MF(KID_B_MASS, k), radius_of(p, A), A};
+}
+// update_verlet_position (IB:6786-6822, IB:7684-7764): the position after dt with the velocity u + dt/2 (axn + bxn),
+// on the tangent plane near the pole
+__device__ __forceinline__ LonLat verlet_position(const DevGrid &g, const kid_params &p, double lon1, double lat1, double uvel1, double vvel1,
+                                                  double axn, double ayn, double bxn, double byn, double dt) {
+  const double dt_2 = 0.5 * dt;
+  const double uvel2 = uvel1 + (dt_2 * axn) + (dt_2 * bxn), vvel2 = vvel1 + (dt_2 * ayn) + (dt_2 * byn);
+  double lonn, latn;
+  if ((lat1 > 89.) && g.latlon) {
+    double x1, y1, xdot2, ydot2;
+    rotpos_to_tang(p, lon1, lat1, x1, y1);
+    rotvec_to_tang(p, lon1, uvel2, vvel2, xdot2, ydot2);
+    rotpos_from_tang(p, x1 + (dt * xdot2), y1 + (dt * ydot2), lonn, latn);
+  } else {
+    double dxdl1, dydl;
+    if (g.latlon) { dxdl1 = (180. / p.pi) / (p.Rearth * cos((lat1) * (p.pi / 180.))); dydl = (180. / p.pi) / p.Rearth; } else { dxdl1 = 1.; dydl = 1.; }
+    const double u2 = uvel2 * dxdl1, v2 = vvel2 * dydl;
+    lonn = lon1 + (dt * u2); latn = lat1 + (dt * v2);
+  }
+  return LonLat{lonn, latn};
+}
+// the *_old velocities MTS leaves after the position update (IB:6826-6827); the v component takes bxn, not byn (sic, IB:6831)
+__device__ __forceinline__ UV mts_old_velocity(double uvel, double vvel, double axn, double ayn, double bxn, double dt_2) {
+  return UV{uvel + dt_2 * (axn + bxn), vvel + dt_2 * (ayn + bxn)};
+}
+// the new velocity uvel3 + dt ax1 (IB:6906-6918, IB:7272-7281), on the tangent plane near the pole
+__device__ __forceinline__ UV verlet_velocity(const DevGrid &g, const kid_params &p, double lonn, double latn, double uvel3, double vvel3,
+                                              double ax1, double ay1, double dt) {
+  double uveln, vveln;
+  if ((latn > 89.) && g.latlon) {
+    double xdot3, ydot3, xddot1, yddot1;
+    rotvec_to_tang(p, lonn, uvel3, vvel3, xdot3, ydot3);
+    rotvec_to_tang(p, lonn, ax1, ay1, xddot1, yddot1);
+    rotvec_from_tang(p, lonn, xdot3 + (dt * xddot1), ydot3 + (dt * yddot1), uveln, vveln);
+  } else { uveln = uvel3 + (dt * ax1); vveln = vvel3 + (dt * ay1); }
+  return UV{uveln, vveln};
+}
+// accel_explicit_inner_mts after its sums (IB:1861-1947).  With DEM bonds: the bond sums F, Fd, T, T_d as accelerations
+// (rM = 1/M, rI = 1/I, I = M R^2 / 2) added to IA, IAd; start_lon matters to the beam tests only.
+struct DemAccel { double IA_x, IA_y, IAd_x, IAd_y, ang_accel; };
+__device__ __forceinline__ DemAccel dem_bond_accel(const kid_params &p, double IA_x, double IA_y, double IAd_x, double IAd_y, double F_x, double F_y,
+                                                   double Fd_x, double Fd_y, double Tq, double T_d, double start_lon, Rcp rM, Rcp rI) {
+  if (p.dem_beam_test > 0) dem_beam_test_load(p, start_lon, F_y, Fd_y);
+  IA_x = IA_x + F_x * rM; IA_y = IA_y + F_y * rM;
+  IAd_x = IAd_x + Fd_x * rM; IAd_y = IAd_y + Fd_y * rM;
+  return DemAccel{IA_x, IA_y, IAd_x, IAd_y, (Tq + T_d) * rI};
+}
+// Then the accelerations from the sums (loc_dx: speed_limit_dx of the berg's cell, or -1 to look it up)
+struct InnerAccel { double axn, ayn, ax1, ay1; };
+__device__ __forceinline__ InnerAccel explicit_inner_accel(const DevGrid &g, const kid_params &p, const MtsDev &m, double IA_x, double IA_y,
+                                                           double IAd_x, double IAd_y, double gdrag, double u, double v, double u_star, double v_star,
+                                                           int i, int j, double dt, double loc_dx) {
+  double axn = IA_x + IAd_x, ayn = IA_y + IAd_y;
+  double ax1 = 0.5 * (axn + 0.), ay1 = 0.5 * (ayn + 0.);
+  double ul = u_star + dt * ax1, vl = v_star + dt * ay1;
+  speed_limit(g, p, m, i, j, dt, ul, vl, loc_dx);
+  if (p.override_iceberg_velocities) { ax1 = 0.; ay1 = 0.; axn = 0.; ayn = 0.; }
+  if (p.short_step_mts_grounding) {
+    axn = axn + u * gdrag; ayn = ayn + v * gdrag;
+    ax1 = 0.5 * axn; ay1 = 0.5 * ayn;
+  }
+  return InnerAccel{axn, ayn, ax1, ay1};
+}
+
 // PART 3 per sub-step.  POST: the tail of the previous sub-step (IB:6972-7044) fused in front of the position update
 // of this one (IB:6786-6833): both touch only the berg's own row.
 template <bool POST, bool POS>
@@ -670,10 +745,8 @@ __global__ void __launch_bounds__(256) mts_substep_own_kernel(const DevGrid g, c
     if (p.use_grounding_torque) {
       const double gf = groundfrac_of(p, MF(KID_B_OD, k), MF(KID_B_THICKNESS, k));
       if (gf > 0.0) {
-        double MM, R1;
-        if (p.constant_interaction_LW) { MM = p.constant_length * p.constant_width * MF(KID_B_THICKNESS, k) * p.rho_bergs; R1 = radius_of(p, p.constant_length * p.constant_width); }
-        else { MM = MF(KID_B_MASS, k); R1 = radius_of(p, MF(KID_B_LENGTH, k) * MF(KID_B_WIDTH, k)); }
-        gdrag = -p.cdrag_grounding * gf * p.pi * kid_pow(R1, 2.) / MM;
+        const Element e = element_of(p, b, k);
+        gdrag = -p.cdrag_grounding * gf * p.pi * kid_pow(e.R, 2.) / e.M;
       }
     }
     if (p.dem) {
@@ -688,22 +761,12 @@ __global__ void __launch_bounds__(256) mts_substep_own_kernel(const DevGrid g, c
     }
   }
   if (POS) {
-    const bool on_tang = (MF(KID_B_LAT, k) > 89.) && g.latlon;
-    const double lon1 = MF(KID_B_LON, k), lat1 = MF(KID_B_LAT, k);
-    double x1 = 0, y1 = 0, dxdl1, dydl;
-    if (on_tang) rotpos_to_tang(p, lon1, lat1, x1, y1);
-    if (g.latlon) { dxdl1 = (180. / p.pi) / (p.Rearth * cos((lat1) * (p.pi / 180.))); dydl = (180. / p.pi) / p.Rearth; } else { dxdl1 = 1.; dydl = 1.; }
     const double uvel1 = MF(KID_B_UVEL, k), vvel1 = MF(KID_B_VVEL, k);
     const double axn = MF(KID_B_AXN_FAST, k), ayn = MF(KID_B_AYN_FAST, k), bxn = MF(KID_B_BXN_FAST, k), byn = MF(KID_B_BYN_FAST, k);
-    const double uvel2 = uvel1 + (dt_2 * axn) + (dt_2 * bxn), vvel2 = vvel1 + (dt_2 * ayn) + (dt_2 * byn);
-    double xdot2 = 0, ydot2 = 0, lonn, latn;
-    if (on_tang) rotvec_to_tang(p, lon1, uvel2, vvel2, xdot2, ydot2);
-    const double u2 = uvel2 * dxdl1, v2 = vvel2 * dydl;
-    if (on_tang) rotpos_from_tang(p, x1 + (dt * xdot2), y1 + (dt * ydot2), lonn, latn);
-    else { lonn = lon1 + (dt * u2); latn = lat1 + (dt * v2); }
-    MF(KID_B_LON, k) = lonn; MF(KID_B_LAT, k) = latn; MF(KID_B_LON_OLD, k) = lonn; MF(KID_B_LAT_OLD, k) = latn;
-    MF(KID_B_UVEL_OLD, k) = uvel1 + dt_2 * (axn + bxn);
-    MF(KID_B_VVEL_OLD, k) = vvel1 + dt_2 * (ayn + bxn);  // sic: bxn_fast, IB:6831
+    const UV old = mts_old_velocity(uvel1, vvel1, axn, ayn, bxn, dt_2);
+    MF(KID_B_UVEL_OLD, k) = old.u; MF(KID_B_VVEL_OLD, k) = old.v;
+    const LonLat q = verlet_position(g, p, MF(KID_B_LON, k), MF(KID_B_LAT, k), uvel1, vvel1, axn, ayn, bxn, byn, dt);
+    MF(KID_B_LON, k) = q.lon; MF(KID_B_LAT, k) = q.lat; MF(KID_B_LON_OLD, k) = q.lon; MF(KID_B_LAT_OLD, k) = q.lat;
   }
 }
 
@@ -829,54 +892,37 @@ __global__ void __launch_bounds__(256) mts_velocity_kernel(const DevGrid g, cons
       }
     }
     if (p.dem) {
-      if (p.dem_beam_test > 0) dem_beam_test_load(p, MF(KID_B_START_LON, k), F_y, Fd_y);
-      double M, R1;
-      if (p.constant_interaction_LW) { M = p.constant_length * p.constant_width * MF(KID_B_THICKNESS, k) * p.rho_bergs; R1 = radius_of(p, p.constant_length * p.constant_width); }
-      else { M = MF(KID_B_MASS, k); R1 = radius_of(p, MF(KID_B_LENGTH, k) * MF(KID_B_WIDTH, k)); }
-      const Rcp rM = kid_rcp(M);
-      IA_x = IA_x + F_x * rM; IA_y = IA_y + F_y * rM;
-      IAd_x = IAd_x + Fd_x * rM; IAd_y = IAd_y + Fd_y * rM;
-      MF(KID_B_ANG_ACCEL, k) = (Tq + T_d) * kid_rcp(0.5 * M * kid_pow(R1, 2.));
+      const Element e = element_of(p, b, k);
+      const DemAccel d = dem_bond_accel(p, IA_x, IA_y, IAd_x, IAd_y, F_x, F_y, Fd_x, Fd_y, Tq, T_d, p.dem_beam_test > 0 ? MF(KID_B_START_LON, k) : 0.,
+                                        kid_rcp(e.M), kid_rcp(0.5 * e.M * kid_pow(e.R, 2.)));
+      IA_x = d.IA_x; IA_y = d.IA_y; IAd_x = d.IAd_x; IAd_y = d.IAd_y;
+      MF(KID_B_ANG_ACCEL, k) = d.ang_accel;
     }
-    axn = IA_x + IAd_x; ayn = IA_y + IAd_y;
-    ax1 = 0.5 * (axn + 0.); ay1 = 0.5 * (ayn + 0.);
-    double ul = u_star + dt * ax1, vl = v_star + dt * ay1;
-    speed_limit(g, p, m, i, j, dt, ul, vl);
-    if (p.override_iceberg_velocities) { ax1 = 0.; ay1 = 0.; axn = 0.; ayn = 0.; }
-    bxn = 0.; byn = 0.;
+    double gdrag = 0.;
     if (p.short_step_mts_grounding) {
       const double gf = groundfrac_of(p, MF(KID_B_OD, k), MF(KID_B_THICKNESS, k));
-      double gdrag = 0.;
       if (gf > 0.0) {
-        double MM, AA;
-        if (p.constant_interaction_LW) { MM = p.constant_length * p.constant_width * MF(KID_B_THICKNESS, k) * p.rho_bergs; AA = p.constant_width * p.constant_length; }
-        else { MM = MF(KID_B_MASS, k); AA = MF(KID_B_LENGTH, k) * MF(KID_B_WIDTH, k); }
-        gdrag = -p.cdrag_grounding * gf * AA / MM;
+        const Element e = element_of(p, b, k);
+        gdrag = -p.cdrag_grounding * gf * e.A / e.M;
       }
-      axn = axn + uvel1 * gdrag; ayn = ayn + vvel1 * gdrag;
-      ax1 = 0.5 * axn; ay1 = 0.5 * ayn;
     }
+    const InnerAccel a = explicit_inner_accel(g, p, m, IA_x, IA_y, IAd_x, IAd_y, gdrag, uvel1, vvel1, u_star, v_star, i, j, dt, -1.);
+    axn = a.axn; ayn = a.ayn; ax1 = a.ax1; ay1 = a.ay1;
+    bxn = 0.; byn = 0.;
   } else {
     double u0 = uvel1, v0 = vvel1, fx = 0., fy = 0.;
     accel_mts(g, p, b, m, k, 3, true, i, j, latn, uvel1, vvel1, u0, v0, dt, ax1, ay1, axn, ayn, bxn, byn, fx, fy);
   }
-  double uveln, vveln;
-  const bool on_tang = (latn > 89.) && g.latlon;
-  if (on_tang) {
-    double xdot3, ydot3, xddot1, yddot1;
-    rotvec_to_tang(p, lonn, uvel3, vvel3, xdot3, ydot3);
-    rotvec_to_tang(p, lonn, ax1, ay1, xddot1, yddot1);
-    rotvec_from_tang(p, lonn, xdot3 + (dt * xddot1), ydot3 + (dt * yddot1), uveln, vveln);
-  } else { uveln = uvel3 + (dt * ax1); vveln = vvel3 + (dt * ay1); }
+  const UV vn = verlet_velocity(g, p, lonn, latn, uvel3, vvel3, ax1, ay1, dt);
   if (p.force_convergence && !p.explicit_inner_mts) {  // rare configuration: one atomic per lane is acceptable here
     const double uo_ = MF(KID_B_UVEL_OLD, k), vo_ = MF(KID_B_VVEL_OLD, k);
     if (jj == 1) unsafeAtomicAdd(m.red + MR_USUM, uo_ * uo_ + vo_ * vo_);
-    unsafeAtomicAdd(m.red + MR_USUM1, uveln * uveln + vveln * vveln);
-    unsafeAtomicAdd(m.red + MR_USUM2, (uveln - uo_) * (uveln - uo_) + (vveln - vo_) * (vveln - vo_));
+    unsafeAtomicAdd(m.red + MR_USUM1, vn.u * vn.u + vn.v * vn.v);
+    unsafeAtomicAdd(m.red + MR_USUM2, (vn.u - uo_) * (vn.u - uo_) + (vn.v - vo_) * (vn.v - vo_));
   }
   MF(KID_B_AXN_FAST, k) = axn; MF(KID_B_AYN_FAST, k) = ayn; MF(KID_B_BXN_FAST, k) = bxn; MF(KID_B_BYN_FAST, k) = byn;
   // a neighbour may still be reading uvel_old/vvel_old of this berg, never uvel/vvel: safe to write in place
-  MF(KID_B_UVEL, k) = uveln; MF(KID_B_VVEL, k) = vveln;
+  MF(KID_B_UVEL, k) = vn.u; MF(KID_B_VVEL, k) = vn.v;
 }
 // ---------------------------------------------------------------------------------------------------------------------
 // The whole sub-step loop of PART 3 (IB:6788-7050) in ONE launch, for the configuration the DEM tests run (explicit inner steps,
@@ -977,15 +1023,14 @@ __global__ void __launch_bounds__(MTS_FUSED_BS) mts_substeps_kernel(const DevGri
     ci_ = MI(KID_BI_INE, kk); cj_ = MI(KID_BI_JNE, kk);
     if (p.dem_beam_test > 0) start_lon = MF(KID_B_START_LON, kk);
     if ((p.speed_limit > 0.) || (p.speed_limit == -1.)) loc_dx = speed_limit_dx(g, ci_, cj_);
-    double R1, AA;
-    if (p.constant_interaction_LW) { AA = p.constant_width * p.constant_length; M = p.constant_length * p.constant_width * MF(KID_B_THICKNESS, kk) * p.rho_bergs; R1 = radius_of(p, p.constant_length * p.constant_width); }
-    else { AA = MF(KID_B_LENGTH, kk) * MF(KID_B_WIDTH, kk); M = MF(KID_B_MASS, kk); R1 = radius_of(p, AA); }
-    I_rot = 0.5 * M * kid_pow(R1, 2.);
+    const Element e = element_of(p, b, kk);
+    M = e.M;
+    I_rot = 0.5 * M * kid_pow(e.R, 2.);
     if (p.short_step_mts_grounding || p.use_grounding_torque) {
       const double gf = groundfrac_of(p, MF(KID_B_OD, kk), MF(KID_B_THICKNESS, kk));
       if (gf > 0.0) {
-        if (p.short_step_mts_grounding) gdrag = -p.cdrag_grounding * gf * AA / M;
-        if (p.use_grounding_torque) gdrag_t = -p.cdrag_grounding * gf * p.pi * kid_pow(R1, 2.) / M;
+        if (p.short_step_mts_grounding) gdrag = -p.cdrag_grounding * gf * e.A / M;
+        if (p.use_grounding_torque) gdrag_t = -p.cdrag_grounding * gf * p.pi * kid_pow(e.R, 2.) / M;
       }
     }
   }
@@ -1113,7 +1158,7 @@ __global__ void __launch_bounds__(MTS_FUSED_BS) mts_substeps_kernel(const DevGri
     KID_TICK_ANY(1);
     if (act_k) {
       // ---- the rest of the velocity sweep of this berg (mts_velocity_kernel, explicit inner step with DEM bonds) ----
-      double axn = axf + bxf, ayn = ayf + byf;
+      const double axn = axf + bxf, ayn = ayf + byf;
       const double uvel3 = uvel + (dt_2 * axn), vvel3 = vvel + (dt_2 * ayn);
       const double u_star = uvel + (axn * (dt / 2.)), v_star = vvel + (ayn * (dt / 2.));
       double IA_x = 0., IA_y = 0., IAd_x = 0., IAd_y = 0.;
@@ -1123,48 +1168,22 @@ __global__ void __launch_bounds__(MTS_FUSED_BS) mts_substeps_kernel(const DevGri
         if (o[s] < 0) { unsafeAtomicAdd(m.red + MR_NERR, 1.); continue; }
         if (br[s] == 1 && !((fresh >> s) & 1)) unbonded_dem_force(g, p, b, m, own, nb[s], kk, o[s], IA_x, IA_y, IAd_x, IAd_y, uvel, vvel, uvel, vvel);
       }
-      if (p.dem_beam_test > 0) dem_beam_test_load(p, start_lon, F_y, Fd_y);
-      IA_x = IA_x + F_x * rM; IA_y = IA_y + F_y * rM;
-      IAd_x = IAd_x + Fd_x * rM; IAd_y = IAd_y + Fd_y * rM;
-      ang_accel = (Tq + T_d) * rI;
-      axn = IA_x + IAd_x; ayn = IA_y + IAd_y;
-      double ax1 = 0.5 * (axn + 0.), ay1 = 0.5 * (ayn + 0.);
-      double ul = u_star + dt * ax1, vl = v_star + dt * ay1;
-      speed_limit(g, p, m, ci_, cj_, dt, ul, vl, loc_dx);
-      if (p.override_iceberg_velocities) { ax1 = 0.; ay1 = 0.; axn = 0.; ayn = 0.; }
-      const double bxn = 0., byn = 0.;
-      if (p.short_step_mts_grounding) {
-        axn = axn + uvel * gdrag; ayn = ayn + vvel * gdrag;
-        ax1 = 0.5 * axn; ay1 = 0.5 * ayn;
-      }
-      double uveln, vveln;
-      const bool on_tang = (lat > 89.) && g.latlon;
-      if (on_tang) {
-        double xdot3, ydot3, xddot1, yddot1;
-        rotvec_to_tang(p, lon, uvel3, vvel3, xdot3, ydot3);
-        rotvec_to_tang(p, lon, ax1, ay1, xddot1, yddot1);
-        rotvec_from_tang(p, lon, xdot3 + (dt * xddot1), ydot3 + (dt * yddot1), uveln, vveln);
-      } else { uveln = uvel3 + (dt * ax1); vveln = vvel3 + (dt * ay1); }
-      axf = axn; ayf = ayn; bxf = bxn; byf = byn; uvel = uveln; vvel = vveln;
+      const DemAccel d = dem_bond_accel(p, IA_x, IA_y, IAd_x, IAd_y, F_x, F_y, Fd_x, Fd_y, Tq, T_d, start_lon, rM, rI);
+      ang_accel = d.ang_accel;
+      const InnerAccel a = explicit_inner_accel(g, p, m, d.IA_x, d.IA_y, d.IAd_x, d.IAd_y, gdrag, uvel, vvel, u_star, v_star, ci_, cj_, dt, loc_dx);
+      const UV vn = verlet_velocity(g, p, lon, lat, uvel3, vvel3, a.ax1, a.ay1, dt);
+      axf = a.axn; ayf = a.ayn; bxf = 0.; byf = 0.; uvel = vn.u; vvel = vn.v;   // (bxn = byn = 0 in the explicit inner step)
       // ---- the berg's own-row tail of this sub-step (IB:6972-7044) and the position update of the next (IB:6786-6833) ----
       double w = own.w + dt * ang_accel;
       w = w * rw;
       own.w = w; own.rot = own.rot + dt * w;
       if (!last) {
-        double x1 = 0, y1 = 0, dxdl1, dydl;
-        if (on_tang) rotpos_to_tang(p, lon, lat, x1, y1);
-        if (g.latlon) { dxdl1 = (180. / p.pi) / (p.Rearth * cos((lat) * (p.pi / 180.))); dydl = (180. / p.pi) / p.Rearth; } else { dxdl1 = 1.; dydl = 1.; }
-        const double uvel2 = uveln + (dt_2 * axn) + (dt_2 * bxn), vvel2 = vveln + (dt_2 * ayn) + (dt_2 * byn);
-        double xdot2 = 0, ydot2 = 0, lon2, lat2;
-        if (on_tang) rotvec_to_tang(p, lon, uvel2, vvel2, xdot2, ydot2);
-        const double u2 = uvel2 * dxdl1, v2 = vvel2 * dydl;
-        if (on_tang) rotpos_from_tang(p, x1 + (dt * xdot2), y1 + (dt * ydot2), lon2, lat2);
-        else { lon2 = lon + (dt * u2); lat2 = lat + (dt * v2); }
-        lon = lon2; lat = lat2;
-        own.lon = lon2; own.lat = lat2;
-        own.u = uveln + dt_2 * (axn + bxn);
-        own.v = vveln + dt_2 * (ayn + bxn);  // sic: bxn_fast, IB:6831
-      } else { own.u = uveln; own.v = vveln; }   // after the last sub-step only the tail: uvel_old = uvel (IB:6974), positions unchanged
+        const LonLat q = verlet_position(g, p, lon, lat, vn.u, vn.v, a.axn, a.ayn, 0., 0., dt);
+        lon = q.lon; lat = q.lat;
+        own.lon = q.lon; own.lat = q.lat;
+        const UV old = mts_old_velocity(vn.u, vn.v, a.axn, a.ayn, 0., dt_2);
+        own.u = old.u; own.v = old.v;
+      } else { own.u = vn.u; own.v = vn.v; }   // after the last sub-step only the tail: uvel_old = uvel (IB:6974), positions unchanged
     }
     KID_TICK_ANY(2);
     if (last) break;                                  // nobody reads the records of the last sub-step
@@ -1622,13 +1641,8 @@ __global__ void __launch_bounds__(256) sts_ia_velocity_kernel(const DevGrid g, c
   }
   double ax1, ay1;
   accel_sts_ia(g, p, b, m, k, e, i, j, latn, uvel1, vvel1, uvel1, vvel1, dt, ax1, ay1, axn, ayn, bxn, byn);
-  double uveln, vveln;
-  if ((latn > 89.) && g.latlon) {
-    double xdot3, ydot3, xddot1, yddot1;
-    rotvec_to_tang(p, lonn, uvel3, vvel3, xdot3, ydot3);
-    rotvec_to_tang(p, lonn, ax1, ay1, xddot1, yddot1);
-    rotvec_from_tang(p, lonn, xdot3 + (dt * xddot1), ydot3 + (dt * yddot1), uveln, vveln);
-  } else { uveln = uvel3 + (dt * ax1); vveln = vvel3 + (dt * ay1); }
+  const UV vn = verlet_velocity(g, p, lonn, latn, uvel3, vvel3, ax1, ay1, dt);
+  double uveln = vn.u, vveln = vn.v;
   if (p.override_iceberg_velocities) { uveln = p.u_override; vveln = p.v_override; }
   MF(KID_B_AXN, k) = axn; MF(KID_B_AYN, k) = ayn; MF(KID_B_BXN, k) = bxn; MF(KID_B_BYN, k) = byn;
   // neighbours read uvel_old / vvel_old, never uvel / vvel: safe to write in place
@@ -1641,20 +1655,9 @@ __global__ void __launch_bounds__(256) sts_ia_position_kernel(const DevGrid g, c
   if (k >= n) return;
   const BergPtrs &b = *bt; const kid_params &p = *pp; const MtsDev &m = *mt;
   if (MI(KID_BI_ALIVE, k) == 0 || !(MF(KID_B_STATIC_BERG, k) < 0.5)) return;
-  const double dt = p.dt, dt_2 = 0.5 * dt;
-  const double lon1 = MF(KID_B_LON, k), lat1 = MF(KID_B_LAT, k);
-  const bool on_tang = (lat1 > 89.) && g.latlon;
-  double x1 = 0, y1 = 0, dxdl1, dydl;
-  if (on_tang) rotpos_to_tang(p, lon1, lat1, x1, y1);
-  if (g.latlon) { dxdl1 = (180. / p.pi) / (p.Rearth * cos((lat1) * (p.pi / 180.))); dydl = (180. / p.pi) / p.Rearth; } else { dxdl1 = 1.; dydl = 1.; }
   const double uvel1 = MF(KID_B_UVEL, k), vvel1 = MF(KID_B_VVEL, k);
-  const double axn = MF(KID_B_AXN, k), ayn = MF(KID_B_AYN, k), bxn = MF(KID_B_BXN, k), byn = MF(KID_B_BYN, k);
-  const double uvel2 = uvel1 + (dt_2 * axn) + (dt_2 * bxn), vvel2 = vvel1 + (dt_2 * ayn) + (dt_2 * byn);
-  double xdot2 = 0, ydot2 = 0, lonn, latn;
-  if (on_tang) rotvec_to_tang(p, lon1, uvel2, vvel2, xdot2, ydot2);
-  const double u2 = uvel2 * dxdl1, v2 = vvel2 * dydl;
-  if (on_tang) rotpos_from_tang(p, x1 + (dt * xdot2), y1 + (dt * ydot2), lonn, latn);
-  else { lonn = lon1 + (dt * u2); latn = lat1 + (dt * v2); }
+  const LonLat q = verlet_position(g, p, MF(KID_B_LON, k), MF(KID_B_LAT, k), uvel1, vvel1, MF(KID_B_AXN, k), MF(KID_B_AYN, k), MF(KID_B_BXN, k), MF(KID_B_BYN, k), p.dt);
+  double lonn = q.lon, latn = q.lat;
   int i = MI(KID_BI_INE, k), j = MI(KID_BI_JNE, k), err = 0;
   double xi = MF(KID_B_XI, k), yj = MF(KID_B_YJ, k);
   bool bail = false;

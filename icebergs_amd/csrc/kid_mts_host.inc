@@ -37,6 +37,10 @@ static int mts_ensure(kid_handle *h, int mb) {
   KID_HIP(h, hipDeviceSynchronize());  // null-stream fills above vs the handle's non-blocking stream (see kid_create)
   return KID_OK;
 }
+// the tables with the namelist's max_bonds slots (at least one), unless they exist already
+static int mts_ensure_default(kid_handle *h) {
+  return h->mts_ready ? KID_OK : mts_ensure(h, h->params.max_bonds > 0 ? h->params.max_bonds : 1);
+}
 static void mts_free(kid_handle *h) {
   if (h->sub_graph_exec) { (void)hipGraphExecDestroy(h->sub_graph_exec); h->sub_graph_exec = nullptr; }
   if (!h->mts_ready) return;
@@ -244,7 +248,7 @@ static int mts_break_bonds(kid_handle *h, int only_if_detected) {
 int kid_set_conglom_ids(kid_handle *h) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
-  int rc = mts_ensure(h, h->mts_ready ? h->mb : (h->params.max_bonds > 0 ? h->params.max_bonds : 1));
+  int rc = mts_ensure_default(h);
   if (rc) return rc;
   const long long n = h->n;
   if (n == 0) return KID_OK;
@@ -296,26 +300,103 @@ int kid_set_conglom_ids(kid_handle *h) {
 
 static int mts_fold_scalars(kid_handle *h);
 
-// evolve_icebergs_mts (IB:6576-7078)
-int kid_evolve_icebergs_mts(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  if (!h->params.mts) { h->err = "kid_evolve_icebergs_mts needs mts=T"; return KID_EINVAL; }
+// what kid_evolve_icebergs_mts and kid_evolve_icebergs_interactive do before their sweeps, when there are bergs
+static int mts_prologue(kid_handle *h) {
   KID_HIP(h, hipSetDevice(h->device));
-  const kid_params &p = h->params;
-  int rc = mts_ensure(h, h->mts_ready ? h->mb : (p.max_bonds > 0 ? p.max_bonds : 1));
+  int rc = mts_ensure_default(h);
   if (rc) return rc;
-  if (p.iceberg_bonds_on && !h->have_bonds) { h->err = "iceberg_bonds_on but no bonds were uploaded (kid_upload_bonds)"; return KID_EINVAL; }
-  const long long n = h->n;
-  if (n == 0) return KID_OK;
+  if (h->params.iceberg_bonds_on && !h->have_bonds) { h->err = "iceberg_bonds_on but no bonds were uploaded (kid_upload_bonds)"; return KID_EINVAL; }
+  if (h->n == 0) return KID_OK;
   rc = mts_build_order(h);
   if (rc) return rc;
   rc = mts_refresh(h);
   if (rc) return rc;
+  hipLaunchKernelGGL(cell_conglom_kernel, dim3((unsigned)((h->ncell + 255) / 256)), dim3(256), 0, h->stream, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, (int)h->ncell);
+  return KID_OK;
+}
+// the convergence test of the implicit iterations of PART 1 and PART 3; usum: the norm of the previous iterate
+static bool mts_converged(const kid_params &p, double usum, const double *red) {
+  const double denom = sqrt(usum) + sqrt(red[MR_USUM1]);
+  const double normchange = denom > 0 ? 2.0 * sqrt(red[MR_USUM2]) / denom : 0.0;
+  return normchange < p.convergence_tolerance;
+}
+// sub-steps first..last of PART 3 (IB:6788-7050) as plain launches, from after the position update of sub-step `first`
+static int mts_plain_substeps(kid_handle *h, int first, int last, bool pair_pass, bool inner_iterates, bool break_each) {
+  const DevGrid g = dev_grid(h);
+  const BergPtrs *bt = h->d_bp; const MtsDev *mt = h->d_mts; const kid_params *pp = h->d_params;
+  const long long n = h->n;
+  int rc;
+  for (int sub = first; sub <= last; ++sub) {
+    if (break_each) { rc = mts_zero_red(h, MR_BREAK, 1); if (rc) return rc; }
+    if (!inner_iterates) {
+      if (pair_pass) hipLaunchKernelGGL(bond_pass_kernel, MTS_GRID(n * h->mb), g, pp, bt, mt, n, h->mts.mts_fast_dt);
+      hipLaunchKernelGGL(mts_velocity_kernel, MTS_GRID(n), g, pp, bt, mt, n, 1);
+    } else {
+      double usum = 0., red[MR_COUNT];
+      rc = mts_zero_red(h, MR_USUM, 3);
+      if (rc) return rc;
+      for (int jj = 1;; ++jj) {   // until converged (the iterate that converges is the last one), or 1001 iterations
+        hipLaunchKernelGGL(mts_velocity_kernel, MTS_GRID(n), g, pp, bt, mt, n, jj);
+        rc = mts_read_red(h, red);
+        if (rc) return rc;
+        if (jj == 1) usum = red[MR_USUM];
+        if ((jj > 1 && mts_converged(h->params, usum, red)) || jj > 1000) break;
+        usum = red[MR_USUM1];
+        hipLaunchKernelGGL(mts_inner_retry_kernel, MTS_GRID(n), bt, mt, n);
+        rc = mts_zero_red(h, MR_USUM1, 2);
+        if (rc) return rc;
+      }
+    }
+    if (break_each) { rc = mts_break_bonds(h, 1); if (rc) return rc; }
+    if (sub < h->params.mts_sub_steps) hipLaunchKernelGGL((mts_substep_own_kernel<true, true>), MTS_GRID(n), g, pp, bt, mt, n);
+    else hipLaunchKernelGGL((mts_substep_own_kernel<true, false>), MTS_GRID(n), g, pp, bt, mt, n);
+  }
+  return KID_OK;
+}
+
+// The whole sub-step loop as one cooperative launch of mts_substeps_kernel, from after the position update of the first
+// sub-step; `enqueued` stays false when not all the bergs' lanes would be co-resident.  A launch the runtime refuses halves
+// the estimate for the next step and this step takes the plain launches.
+static int mts_fused_substeps(kid_handle *h, bool &enqueued) {
+  const long long n = h->n;
+  const bool g4 = h->mb <= 4;
+  const void *fn = g4 ? (const void *)mts_substeps_kernel<4> : (const void *)mts_substeps_kernel<8>;
+  int &fused_blocks = h->fused_blocks[g4 ? 0 : 1];   // (per kernel variant: <4> and <8> differ in registers, i.e. in occupancy)
+  if (fused_blocks == 0) {   // how many workgroups are co-resident (the cooperative launch checks it again)
+    int per_cu = 0, ncu = 0;
+    KID_HIP(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, MTS_FUSED_BS, 0));
+    KID_HIP(h, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+    fused_blocks = std::max(1, std::min(per_cu, 4)) * std::max(1, ncu);
+    if (h->dbg.mts_fused_blocks_cap > 0) fused_blocks = std::min(fused_blocks, h->dbg.mts_fused_blocks_cap);
+  }
+  const long long need_blocks = (n + MTS_FUSED_BS - 1) / MTS_FUSED_BS;
+  if (need_blocks > (long long)fused_blocks) return KID_OK;   // one lane per berg, all co-resident; a bigger population fills the chip with the three-launch graph
+  enqueued = true;
+  KID_HIP(h, hipMemsetD32Async((hipDeviceptr_t)h->mts.rec, (int)0xfff7c0deu, (size_t)3 * 16 * (size_t)n, h->stream));   // every record of the three copies: not yet written
+  DevGrid g_arg = dev_grid(h); const kid_params *pp_arg = h->d_params; const BergPtrs *bt_arg = h->d_bp; const MtsDev *mt_arg = h->d_mts;
+  long long n_arg = n; int nsub_arg = h->params.mts_sub_steps;
+  int poll_arg = h->dbg.mts_poll_limit > 0 ? h->dbg.mts_poll_limit : (int)MTS_POLL_LIMIT; int *to_arg = h->d_order_flag + 2;
+  void *args[] = {&g_arg, &pp_arg, &bt_arg, &mt_arg, &n_arg, &nsub_arg, &poll_arg, &to_arg};
+  const hipError_t e = hipLaunchCooperativeKernel(fn, dim3((unsigned)need_blocks), dim3(MTS_FUSED_BS), args, 0, h->stream);
+  if (e == hipSuccess) { h->fused_ran = true; return KID_OK; }
+  if (e != hipErrorCooperativeLaunchTooLarge) { h->err = std::string("hipLaunchCooperativeKernel: ") + hipGetErrorString(e); return KID_EHIP; }
+  (void)hipGetLastError();
+  fused_blocks = std::max(1, fused_blocks / 2);
+  return mts_plain_substeps(h, 1, h->params.mts_sub_steps, true, false, false);
+}
+
+// evolve_icebergs_mts (IB:6576-7078)
+int kid_evolve_icebergs_mts(kid_handle *h) {
+  if (!h) return KID_EINVAL;
+  if (!h->params.mts) { h->err = "kid_evolve_icebergs_mts needs mts=T"; return KID_EINVAL; }
+  int rc = mts_prologue(h);
+  if (rc || h->n == 0) return rc;
+  const kid_params &p = h->params;
+  const long long n = h->n;
   const DevGrid g = dev_grid(h);
   const BergPtrs *bt = h->d_bp; const MtsDev *mt = h->d_mts; const kid_params *pp = h->d_params;
   rc = mts_zero_red(h, 0, MR_COUNT);
   if (rc) return rc;
-  hipLaunchKernelGGL(cell_conglom_kernel, dim3((unsigned)((h->ncell + 255) / 256)), dim3(256), 0, h->stream, bt, mt, (int)h->ncell);
   double red[MR_COUNT];
   // PART 1
   {
@@ -332,11 +413,7 @@ int kid_evolve_icebergs_mts(kid_handle *h) {
         had_collision = had_collision || red[MR_COLLISION] != 0.;
       }
       if (p.force_convergence && !last_iter && had_collision) {
-        if (ii > 1) {
-          const double denom = sqrt(usum) + sqrt(red[MR_USUM1]);
-          const double normchange = denom > 0 ? 2.0 * sqrt(red[MR_USUM2]) / denom : 0.0;
-          if (normchange < p.convergence_tolerance) last_iter = true;
-        }
+        if (ii > 1 && mts_converged(p, usum, red)) last_iter = true;
         usum = red[MR_USUM1];
       } else finished = true;
       if (last_iter) finished = true;
@@ -354,115 +431,41 @@ int kid_evolve_icebergs_mts(kid_handle *h) {
   // The common configuration (explicit inner steps, no host decision inside the loop) is 3 short launches per sub-step,
   // 90-200 sub-steps per step: captured once into a hipGraph and replayed, so the loop is not bound by launch calls.
   const bool graphable = !inner_iterates && !break_each && h->use_graph;
+  hipLaunchKernelGGL((mts_substep_own_kernel<false, true>), MTS_GRID(n), g, pp, bt, mt, n);   // position update of the first sub-step
   // The DEM configuration of the tests and of config 4 (explicit inner steps, DEM bonds, broken bonds as the only sub-step
   // contacts): the whole loop is one cooperative launch (mts_substeps_kernel); everything else replays the captured graph.
-  bool fused_done = false;
+  bool fused = false;
   if (graphable && pair_pass && p.use_broken_bonds_for_substep_contact && p.mts_sub_steps >= 1 && h->mb <= 8 && !h->dbg.mts_no_fused) {
-    const bool g4 = h->mb <= 4;
-    const void *fn = g4 ? (const void *)mts_substeps_kernel<4> : (const void *)mts_substeps_kernel<8>;
-    int &fused_blocks = h->fused_blocks[g4 ? 0 : 1];   // (per kernel variant: <4> and <8> differ in registers, i.e. in occupancy)
-    if (fused_blocks == 0) {   // how many workgroups are co-resident (the cooperative launch checks it again)
-      int per_cu = 0, ncu = 0;
-      KID_HIP(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, MTS_FUSED_BS, 0));
-      KID_HIP(h, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-      fused_blocks = std::max(1, std::min(per_cu, 4)) * std::max(1, ncu);
-      if (h->dbg.mts_fused_blocks_cap > 0) fused_blocks = std::min(fused_blocks, h->dbg.mts_fused_blocks_cap);
-    }
-    const long long need_blocks = (n + MTS_FUSED_BS - 1) / MTS_FUSED_BS;
-    const unsigned nblocks = (unsigned)need_blocks;
-    if (need_blocks > (long long)fused_blocks) goto not_fused;   // one lane per berg, all co-resident; a bigger population fills the chip with the plain launches
-    hipLaunchKernelGGL((mts_substep_own_kernel<false, true>), MTS_GRID(n), g, pp, bt, mt, n);                       // position update of the first sub-step
-    KID_HIP(h, hipMemsetD32Async((hipDeviceptr_t)h->mts.rec, (int)0xfff7c0deu, (size_t)3 * 16 * (size_t)n, h->stream));   // every record of the three copies: not yet written
-    DevGrid g_arg = g; const kid_params *pp_arg = pp; const BergPtrs *bt_arg = bt; const MtsDev *mt_arg = mt; long long n_arg = n; int nsub_arg = p.mts_sub_steps;
-    int poll_arg = h->dbg.mts_poll_limit > 0 ? h->dbg.mts_poll_limit : (int)MTS_POLL_LIMIT; int *to_arg = h->d_order_flag + 2;
-    void *args[] = {&g_arg, &pp_arg, &bt_arg, &mt_arg, &n_arg, &nsub_arg, &poll_arg, &to_arg};
-    const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(nblocks), dim3(MTS_FUSED_BS), args, 0, h->stream);
-    if (e == hipSuccess) { fused_done = true; h->fused_ran = true; }
-    else if (e == hipErrorCooperativeLaunchTooLarge) { (void)hipGetLastError(); fused_blocks = std::max(1, fused_blocks / 2); }   // retry smaller next step; this step takes the graph
-    else { h->err = std::string("hipLaunchCooperativeKernel: ") + hipGetErrorString(e); return KID_EHIP; }
-    if (!fused_done) {
-      // the first own-row launch has run: finish the step with plain launches
-      for (int sub = 1; sub <= p.mts_sub_steps; ++sub) {
-        if (sub > 1) hipLaunchKernelGGL((mts_substep_own_kernel<true, true>), MTS_GRID(n), g, pp, bt, mt, n);
-        hipLaunchKernelGGL(bond_pass_kernel, MTS_GRID(n * h->mb), g, pp, bt, mt, n, h->mts.mts_fast_dt);
-        hipLaunchKernelGGL(mts_velocity_kernel, MTS_GRID(n), g, pp, bt, mt, n, 1);
-      }
-      hipLaunchKernelGGL((mts_substep_own_kernel<true, false>), MTS_GRID(n), g, pp, bt, mt, n);
-    }
-    hipLaunchKernelGGL(mts_adjust_kernel, MTS_GRID(n), g, pp, bt, mt, n);
-    KID_HIP(h, hipGetLastError());
-    return mts_fold_scalars(h);
+    rc = mts_fused_substeps(h, fused);
+    if (rc) return rc;
   }
-not_fused:
-  if (graphable) {
-    // own(first) | [pair pass, velocity sweep, own] x (N-1) | pair pass, velocity sweep | own(tail, below).  The bracket is
-    // captured once as a graph of at most MTS_GRAPH_UNITS units and replayed; what does not fill a replay is launched plainly
-    // (the beam tests run 1e5 sub-steps per step: one graph of 3e5 nodes is not a reasonable thing to instantiate).
+  int first = 1;   // the sub-steps from `first` on are plain launches
+  if (!fused && graphable && p.mts_sub_steps > 1) {
+    // [pair pass, velocity sweep, own] x (N-1) in graphs of at most MTS_GRAPH_UNITS units, the rest plainly (the beam tests
+    // run 1e5 sub-steps per step: one graph of 3e5 nodes is not a reasonable thing to instantiate)
     enum { MTS_GRAPH_UNITS = 2048 };
     const int units = p.mts_sub_steps - 1, per_graph = std::min(units, (int)MTS_GRAPH_UNITS);
-    auto unit = [&](bool with_own) {
-      if (pair_pass) hipLaunchKernelGGL(bond_pass_kernel, MTS_GRID(n * h->mb), g, pp, bt, mt, n, h->mts.mts_fast_dt);
-      hipLaunchKernelGGL(mts_velocity_kernel, MTS_GRID(n), g, pp, bt, mt, n, 1);
-      if (with_own) hipLaunchKernelGGL((mts_substep_own_kernel<true, true>), MTS_GRID(n), g, pp, bt, mt, n);
-    };
-    hipLaunchKernelGGL((mts_substep_own_kernel<false, true>), MTS_GRID(n), g, pp, bt, mt, n);
-    if (per_graph > 0) {
-      const bool stale = !h->sub_graph_exec || h->sub_graph_n != n || h->sub_graph_steps != per_graph || h->sub_graph_pair != pair_pass ||
-                         h->sub_graph_dt != h->mts.mts_fast_dt || h->sub_graph_stream != h->stream;
-      if (stale) {
-        if (h->sub_graph_exec) { (void)hipGraphExecDestroy(h->sub_graph_exec); h->sub_graph_exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        KID_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        for (int u = 0; u < per_graph; ++u) unit(true);
-        KID_HIP(h, hipStreamEndCapture(h->stream, &graph));
-        KID_HIP(h, hipGraphInstantiate(&h->sub_graph_exec, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-        h->sub_graph_n = n; h->sub_graph_steps = per_graph; h->sub_graph_pair = pair_pass; h->sub_graph_dt = h->mts.mts_fast_dt;
-        h->sub_graph_stream = h->stream;
-      }
-      for (int q = 0; q < units / per_graph; ++q) KID_HIP(h, hipGraphLaunch(h->sub_graph_exec, h->stream));
-      for (int u = 0; u < units % per_graph; ++u) unit(true);
-    }
-    unit(false);
-  }
-  for (int sub = 1; sub <= (graphable ? 0 : p.mts_sub_steps); ++sub) {
-    if (sub == 1) hipLaunchKernelGGL((mts_substep_own_kernel<false, true>), MTS_GRID(n), g, pp, bt, mt, n);
-    else hipLaunchKernelGGL((mts_substep_own_kernel<true, true>), MTS_GRID(n), g, pp, bt, mt, n);
-    if (break_each) { rc = mts_zero_red(h, MR_BREAK, 1); if (rc) return rc; }
-    if (!inner_iterates) {
-      if (pair_pass) hipLaunchKernelGGL(bond_pass_kernel, MTS_GRID(n * h->mb), g, pp, bt, mt, n, h->mts.mts_fast_dt);
-      hipLaunchKernelGGL(mts_velocity_kernel, MTS_GRID(n), g, pp, bt, mt, n, 1);
-    } else {
-      int jj = 0; bool finished = false, last_iter = false;
-      double usum = 0.;
-      rc = mts_zero_red(h, MR_USUM, 3);
+    const bool stale = !h->sub_graph_exec || h->sub_graph_n != n || h->sub_graph_steps != per_graph || h->sub_graph_pair != pair_pass ||
+                       h->sub_graph_dt != h->mts.mts_fast_dt || h->sub_graph_stream != h->stream;
+    if (stale) {
+      if (h->sub_graph_exec) { (void)hipGraphExecDestroy(h->sub_graph_exec); h->sub_graph_exec = nullptr; }
+      hipGraph_t graph = nullptr;
+      KID_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+      rc = mts_plain_substeps(h, 1, per_graph, pair_pass, false, false);
       if (rc) return rc;
-      while (!finished) {
-        ++jj;
-        hipLaunchKernelGGL(mts_velocity_kernel, MTS_GRID(n), g, pp, bt, mt, n, jj);
-        rc = mts_read_red(h, red);
-        if (rc) return rc;
-        if (jj == 1) usum = red[MR_USUM];
-        if (!last_iter) {
-          if (jj > 1) {
-            const double denom = sqrt(usum) + sqrt(red[MR_USUM1]);
-            const double normchange = denom > 0 ? 2.0 * sqrt(red[MR_USUM2]) / denom : 0.0;
-            if (normchange < p.convergence_tolerance) last_iter = true;
-          }
-          usum = red[MR_USUM1];
-        } else finished = true;
-        if (last_iter) finished = true;
-        if (jj > 1000) finished = true;
-        if (!finished) {
-          hipLaunchKernelGGL(mts_inner_retry_kernel, MTS_GRID(n), bt, mt, n);
-          rc = mts_zero_red(h, MR_USUM1, 2);
-          if (rc) return rc;
-        }
-      }
+      KID_HIP(h, hipStreamEndCapture(h->stream, &graph));
+      KID_HIP(h, hipGraphInstantiate(&h->sub_graph_exec, graph, nullptr, nullptr, 0));
+      (void)hipGraphDestroy(graph);
+      h->sub_graph_n = n; h->sub_graph_steps = per_graph; h->sub_graph_pair = pair_pass; h->sub_graph_dt = h->mts.mts_fast_dt;
+      h->sub_graph_stream = h->stream;
     }
-    if (break_each) { rc = mts_break_bonds(h, 1); if (rc) return rc; }
+    for (int q = 0; q < units / per_graph; ++q) KID_HIP(h, hipGraphLaunch(h->sub_graph_exec, h->stream));
+    first += units / per_graph * per_graph;
   }
-  hipLaunchKernelGGL((mts_substep_own_kernel<true, false>), MTS_GRID(n), g, pp, bt, mt, n);
+  if (!fused) {
+    rc = mts_plain_substeps(h, first, p.mts_sub_steps, pair_pass, inner_iterates, break_each);
+    if (rc) return rc;
+  }
   hipLaunchKernelGGL(mts_adjust_kernel, MTS_GRID(n), g, pp, bt, mt, n);
   KID_HIP(h, hipGetLastError());
   return mts_fold_scalars(h);
@@ -489,7 +492,7 @@ static int mts_fold_scalars(kid_handle *h) {
 }
 // quadratic ocean depth at the bergs (IB:4894), after the environment interpolation
 static int mts_depth(kid_handle *h) {
-  int rc = mts_ensure(h, h->mts_ready ? h->mb : (h->params.max_bonds > 0 ? h->params.max_bonds : 1));
+  int rc = mts_ensure_default(h);
   if (rc) return rc;
   if (h->n == 0) return KID_OK;
   if (h->mts_dirty || h->tables_dirty) { rc = mts_refresh(h); if (rc) return rc; }
@@ -503,18 +506,10 @@ int kid_evolve_icebergs_interactive(kid_handle *h) {
   if (!h) return KID_EINVAL;
   const kid_params &p = h->params;
   if (p.mts || !p.interactive_icebergs_on) { h->err = "kid_evolve_icebergs_interactive: needs interactive_icebergs_on and mts=F"; return KID_EINVAL; }
-  KID_HIP(h, hipSetDevice(h->device));
-  int rc = mts_ensure(h, h->mts_ready ? h->mb : (p.max_bonds > 0 ? p.max_bonds : 1));
-  if (rc) return rc;
-  if (p.iceberg_bonds_on && !h->have_bonds) { h->err = "iceberg_bonds_on but no bonds were uploaded (kid_upload_bonds)"; return KID_EINVAL; }
+  int rc = mts_prologue(h);
+  if (rc || h->n == 0) return rc;
   const long long n = h->n;
-  if (n == 0) return KID_OK;
-  rc = mts_build_order(h);
-  if (rc) return rc;
-  rc = mts_refresh(h);
-  if (rc) return rc;
   const DevGrid g = dev_grid(h);
-  hipLaunchKernelGGL(cell_conglom_kernel, dim3((unsigned)((h->ncell + 255) / 256)), dim3(256), 0, h->stream, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, (int)h->ncell);
   hipLaunchKernelGGL(sts_ia_velocity_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
   hipLaunchKernelGGL(sts_ia_position_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
   KID_HIP(h, hipGetLastError());
