@@ -522,7 +522,8 @@ __device__ __forceinline__ bool pos_within_cell(const DevGrid &g, const kid_para
         if (alpha != 0.) xi = kid_div(dx, alpha); else { err = 1; xi = -999.; }
       }
     } else if (!calc_xiyj(q.lon00, q.lon10, q.lon11, q.lon01, q.lat00, q.lat10, q.lat11, q.lat01, x, y, xi, yj, g.Lx)) err = 1;
-    const bool inside = (dmin(xi, yj) > HOT_EDGE) && (dmax(xi, yj) < 1. - HOT_EDGE);
+    // (four compares rather than min / max: the same test for numbers, no canonicalising moves; a NaN now bails)
+    const bool inside = (xi > HOT_EDGE) & (yj > HOT_EDGE) & (xi < 1. - HOT_EDGE) & (yj < 1. - HOT_EDGE);
     if (!inside) bail = true;
     return inside;
   }
@@ -718,10 +719,10 @@ __device__ __forceinline__ void accel(const DevGrid &g, const kid_params &p, con
   if (any_ice) { if (fabs(ui) + fabs(vi) == 0.) c_ice = 0.; }
   const bool has_gnd = Sw<K>::cdrag_grounding(p) != 0.;   // (c_gnd = 0 otherwise, accel_pre)
   (void)has_gnd;
-  const double ex = -GRAVITY * e.ssh_x + wave_rad * uwave, ey = -GRAVITY * e.ssh_y + wave_rad * vwave;  // IB:2142-2149
+  const double ex = kid_fma(wave_rad, uwave, -GRAVITY * e.ssh_x), ey = kid_fma(wave_rad, vwave, -GRAVITY * e.ssh_y);  // IB:2142-2149
   double axn_l, ayn_l, bxn_l, byn_l;
-  if (RK) { axn_l = 0.; ayn_l = 0.; bxn_l = ex + f_cori * vvel; byn_l = ey - f_cori * uvel; }          // IB:2172-2173
-  else    { axn_l = ex + f_cori * v_star; ayn_l = ey - f_cori * u_star; bxn_l = 0.; byn_l = 0.; }      // IB:2165-2166
+  if (RK) { axn_l = 0.; ayn_l = 0.; bxn_l = kid_fma(f_cori, vvel, ex); byn_l = kid_fma(-f_cori, uvel, ey); }          // IB:2172-2173
+  else    { axn_l = kid_fma(f_cori, v_star, ex); ayn_l = kid_fma(-f_cori, u_star, ey); bxn_l = 0.; byn_l = 0.; }      // IB:2165-2166
   double uveln = new_pc ? uvel0 : uvel, vveln = new_pc ? vvel0 : vvel;
   // the |V0 - V_x| halves of the predictive-corrective drag do not change between the two passes
   double s0o = 0., s0a = 0., s0i = 0.;
@@ -761,12 +762,12 @@ __device__ __forceinline__ void accel(const DevGrid &g, const kid_params &p, con
     // the same sums in the same order, without the terms that are 0 times something (RK: axn = 0; no ice in the wave; no
     // grounding drag in the namelist): x - 0 * y = x
     double RHS_x = RK ? bxn_l : (axn_l / 2) + bxn_l, RHS_y = RK ? byn_l : (ayn_l / 2) + byn_l;
-    RHS_x = RHS_x - drag_ocn * (u_star - uo) - drag_atm * (u_star - ua);  // beta=1
-    RHS_y = RHS_y - drag_ocn * (v_star - vo) - drag_atm * (v_star - va);
+    RHS_x = kid_fma(-drag_atm, u_star - ua, kid_fma(-drag_ocn, u_star - uo, RHS_x));  // beta=1
+    RHS_y = kid_fma(-drag_atm, v_star - va, kid_fma(-drag_ocn, v_star - vo, RHS_y));
     double lambda = drag_ocn + drag_atm;
     // (the empty asm keeps each block a branch: speculated, the compiler evaluates the terms anyway and selects)
-    if (any_ice) { asm volatile(""); RHS_x = RHS_x - drag_ice * (u_star - ui); RHS_y = RHS_y - drag_ice * (v_star - vi); lambda = lambda + drag_ice; }
-    if (has_gnd) { asm volatile(""); RHS_x = RHS_x - drag_gnd * u_star; RHS_y = RHS_y - drag_gnd * v_star; lambda = lambda + drag_gnd; }
+    if (any_ice) { asm volatile(""); RHS_x = kid_fma(-drag_ice, u_star - ui, RHS_x); RHS_y = kid_fma(-drag_ice, v_star - vi, RHS_y); lambda = lambda + drag_ice; }
+    if (has_gnd) { asm volatile(""); RHS_x = kid_fma(-drag_gnd, u_star, RHS_x); RHS_y = kid_fma(-drag_gnd, v_star, RHS_y); lambda = lambda + drag_gnd; }
 #endif
     const double A11 = kid_fma(dt, lambda, 1.), A22 = A11;
 #ifdef KID_EXACT_MATH
@@ -786,7 +787,7 @@ __device__ __forceinline__ void accel(const DevGrid &g, const kid_params &p, con
     vveln = kid_fma(dt, ay, v_star);
   }
   if (RK) { axn = 0.; ayn = 0.; }                                               // IB:2286
-  else    { axn = ex + f_cori * vveln; ayn = ey - f_cori * uveln; }              // IB:2288-2297
+  else    { axn = kid_fma(f_cori, vveln, ex); ayn = kid_fma(-f_cori, uveln, ey); }              // IB:2288-2297
   bxn = ax - (axn / 2); byn = ay - (ayn / 2);
   if (Sw<K>::speed_limit(p) > 0. || Sw<K>::speed_limit(p) == -1.) {  // IB:2304-2323: only the ticket counter survives
     const double speed = kid_sqrt(uveln * uveln + vveln * vveln);
@@ -978,7 +979,7 @@ template <bool OLD_ORDER, bool FAST, int K = 0>
 __device__ __forceinline__ void rk4_step(const DevGrid &g, const kid_params &p, const BergGeom &bg, const Env &stored,
                                          BergDyn &d, unsigned &tickets, int &err, bool &bail, const lds_double *pk,
                                          double latref_s = 0., double latref_c = 1.) {
-  const double dt = p.dt, dt_2 = 0.5 * dt, dt_6 = dt / 6.;
+  const double dt = p.dt, dt_2 = 0.5 * dt, dt_6 = kid_div(dt, 6.);
   const double sin_ref = g.sin_lat_ref;
   const double dydl = grid_latlon<K>(g) ? g.dydl : 1.;
   const int i1 = d.ine, j1 = d.jne;
@@ -1060,7 +1061,8 @@ __device__ __forceinline__ void rk4_step(const DevGrid &g, const kid_params &p, 
 #else
     {  // one running sum q1 + 2 q2 + 2 q3 + q4 per quantity (kept in A, B stays 0): half the registers of the (q1+q4), (q2+q3) pairs
       const double wq = (s == 0 || s == 3) ? 1. : 2.;
-      Au = Au + wq * qu; Av = Av + wq * qv; Aax = Aax + wq * qax; Aay = Aay + wq * qay; Aaxn = Aaxn + wq * qaxn; Aayn = Aayn + wq * qayn;
+      // (wq q is exact: the fused sum is the same number)
+      Au = kid_fma(wq, qu, Au); Av = kid_fma(wq, qv, Av); Aax = kid_fma(wq, qax, Aax); Aay = kid_fma(wq, qay, Aay); Aaxn = kid_fma(wq, qaxn, Aaxn); Aayn = kid_fma(wq, qayn, Aayn);
       // (unrolled stages: the sums are formed here and now -- left to itself the scheduler sinks the four additions of every
       // quantity to the end of the step and keeps, or spills, the terms until then)
       if constexpr (FAST) asm volatile("" : "+v"(Au), "+v"(Av), "+v"(Aax), "+v"(Aay));
@@ -1074,13 +1076,19 @@ __device__ __forceinline__ void rk4_step(const DevGrid &g, const kid_params &p, 
         rotpos_from_tang(p, xs, ys, lon_s, lat_s);
         rotvec_from_tang(p, lon_s, xdot_s, ydot_s, uvel_s, vvel_s);
       } else {
-        lon_s = lon1 + c * qu; lat_s = lat1 + c * qv;
-        uvel_s = uvel1 + c * ax; vvel_s = vvel1 + c * ay;
+        lon_s = kid_fma(c, qu, lon1); lat_s = kid_fma(c, qv, lat1);
+        uvel_s = kid_fma(c, ax, uvel1); vvel_s = kid_fma(c, ay, vvel1);
       }
     }
   }
   KID_MARK("loop_end"); KID_TICK(5);
-  // combine IB:7597-7616
+  // combine IB:7597-7616.  Without -DKID_EXACT_MATH the running sums are all in A (B stays 0: x + 2 * 0 is not folded away),
+  // and the divisions by 6 are kid_div's (the reciprocal of the literal is folded: three instructions instead of ten)
+#ifdef KID_EXACT_MATH
+  const auto rk_sum = [](double a, double b) { return a + 2. * b; };
+#else
+  const auto rk_sum = [](double a, double) { return a; };
+#endif
   double lonn, latn, uveln, vveln, axn, ayn;
   if (on_tang) {
     const double xn = x1 + dt_6 * (Au + 2. * Bu), yn = y1 + dt_6 * (Av + 2. * Bv);
@@ -1090,14 +1098,14 @@ __device__ __forceinline__ void rk4_step(const DevGrid &g, const kid_params &p, 
     rotvec_from_tang(p, lonn, xdotn, ydotn, uveln, vveln);
     rotvec_from_tang(p, lonn, xddotn, yddotn, axn, ayn);  // bxn,byn stay as the 4th accel left them
   } else {
-    lonn = lon1 + dt_6 * (Au + 2. * Bu);
-    latn = lat1 + dt_6 * (Av + 2. * Bv);
-    uveln = uvel1 + dt_6 * (Aax + 2. * Bax);
-    vveln = vvel1 + dt_6 * (Aay + 2. * Bay);
-    axn = (Aaxn + 2. * Baxn) / 6.;
-    ayn = (Aayn + 2. * Bayn) / 6.;
-    bxn = ((Aax + 2. * Bax) / 6) - (axn / 2);
-    byn = ((Aay + 2. * Bay) / 6) - (ayn / 2);
+    lonn = kid_fma(dt_6, rk_sum(Au, Bu), lon1);
+    latn = kid_fma(dt_6, rk_sum(Av, Bv), lat1);
+    uveln = kid_fma(dt_6, rk_sum(Aax, Bax), uvel1);
+    vveln = kid_fma(dt_6, rk_sum(Aay, Bay), vvel1);
+    axn = kid_div(rk_sum(Aaxn, Baxn), 6.);
+    ayn = kid_div(rk_sum(Aayn, Bayn), 6.);
+    bxn = kid_div(rk_sum(Aax, Bax), 6.) - (axn / 2);
+    byn = kid_div(rk_sum(Aay, Bay), 6.) - (ayn / 2);
   }
   i = i1; j = j1; xi = xi1; yj = yj1;
   KID_PHASE_FENCE();

@@ -221,16 +221,16 @@ __device__ __forceinline__ void thermodynamics(const DevGrid &g, const kid_param
   const double Vol = T * W * L;
   const Rcp rVol = kid_rcp(Vol);
   double du = uvel - e.uo, dv = vvel - e.vo;
-  const double dvo = kid_sqrt_nn(du * du + dv * dv);
+  const double dvo = kid_sqrt_nn(kid_fma(du, du, dv * dv));
   du = e.ua - e.uo; dv = e.va - e.vo;
-  const double dva = kid_sqrt_nn(du * du + dv * dv);
+  const double dva = kid_sqrt_nn(kid_fma(du, du, dv * dv));
 #ifdef KID_EXACT_MATH
   const double Ss = 1.5 * kid_pow(dva, 0.5) + 0.1 * dva;
 #else
-  const double Ss = 1.5 * kid_sqrt_nn(dva) + 0.1 * dva;   // dva**0.5 (IB:2908)
+  const double Ss = kid_fma(1.5, kid_sqrt_nn(dva), 0.1 * dva);   // dva**0.5 (IB:2908)
 #endif
   const double dvo08 = kid_pow08(dvo);
-  double Mv = dmax(7.62e-3 * SST + 1.29e-3 * (SST * SST), 0.) * perday;
+  double Mv = dmax(kid_fma(7.62e-3, SST, 1.29e-3 * (SST * SST)), 0.) * perday;
   double Mb = dmax(kid_mul_rpow5(0.58 * dvo08 * (SST + 4.0), L), 0.) * perday;
   // cos(pi IC^3): no lane of the wave in sea ice (IC = 0) is the common case, and cos(0) = 1 exactly
   const double cos_ic = (__ballot(IC != 0.) == 0ull) ? 1.0 : cos(p.pi * (IC * IC * IC));
@@ -259,15 +259,15 @@ __device__ __forceinline__ void thermodynamics(const DevGrid &g, const kid_param
   if (Sw<K>::set_melt_rates_to_zero(p)) { Mv = 0.0; Mb = 0.0; Me = 0.0; }
   double Tn, nVol, Mnew, dMb, dMv, dMe, dM, Ln1 = 0., Wn1 = 0., Ln, Wn;
   if (Sw<K>::use_operator_splitting(p)) {  // IB:2976-2994
-    Tn = dmax(T - Mb * dt, 0.);
+    Tn = dmax(kid_fma(-Mb, dt, T), 0.);
     nVol = Tn * W * L; const double Mnew1 = (nVol * rVol) * M; dMb = M - Mnew1;
-    Ln1 = dmax(L - Mv * dt, 0.); Wn1 = dmax(W - Mv * dt, 0.);
+    Ln1 = dmax(kid_fma(-Mv, dt, L), 0.); Wn1 = dmax(kid_fma(-Mv, dt, W), 0.);
     nVol = Tn * Wn1 * Ln1; const double Mnew2 = (nVol * rVol) * M; dMv = Mnew1 - Mnew2;
-    Ln = dmax(Ln1 - Me * dt, 0.); Wn = dmax(Wn1 - Me * dt, 0.);
+    Ln = dmax(kid_fma(-Me, dt, Ln1), 0.); Wn = dmax(kid_fma(-Me, dt, Wn1), 0.);
     nVol = Tn * Wn * Ln; Mnew = (nVol * rVol) * M; dMe = Mnew2 - Mnew;
     dM = M - Mnew;
   } else {
-    Ln = dmax(L - (Mv + Me) * (dt), 0.); Wn = dmax(W - (Mv + Me) * (dt), 0.); Tn = dmax(T - Mb * (dt), 0.);
+    Ln = dmax(kid_fma(-(Mv + Me), dt, L), 0.); Wn = dmax(kid_fma(-(Mv + Me), dt, W), 0.); Tn = dmax(kid_fma(-Mb, dt, T), 0.);
     nVol = Tn * Wn * Ln; Mnew = (nVol * rVol) * M; dM = M - Mnew;
     dMb = (M * rVol) * (W * L) * Mb * dt;
     dMe = (M * rVol) * (T * (W + L)) * Me * dt;
