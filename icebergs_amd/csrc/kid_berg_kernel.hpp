@@ -69,8 +69,12 @@ template <int K> struct Fl {
 #ifndef KID_GENERAL_WAVES_PER_EU
 #define KID_GENERAL_WAVES_PER_EU 2   // <=256 registers: a general-build wave can share a SIMD with a hot-build wave (pipelined mode)
 #endif
+// Where the staging instance (STAGE = true, kid_set_reproducible_sums) puts a row's contributions (StageSeg, kid_thermo.hpp):
+// val[slot * cap + row]; key[row] = the cell it contributed to (-1: none in this launch); mask[row] = the slots it wrote.
+struct StageTab { double *val; int32_t *key; unsigned long long *mask; long long cap; };
 struct Redo { int *list; int *count; long long k0, klen; int *lane; int step;    // k0, klen: the rows the hot build covers in this launch
-              int *fl_cursor; int32_t *fl_counter; long long fl_capacity; int fl_iNg; unsigned fl_step; };   // PH_FL: where footloose children go (FlChildCtx)
+              int *fl_cursor; int32_t *fl_counter; long long fl_capacity; int fl_iNg; unsigned fl_step;   // PH_FL: where footloose children go (FlChildCtx)
+              StageTab st{}; };
 // lane/step ("slow lane" schedule, launch_berg_lanes): lane[k] >= step means berg k is owned by general-build launches that
 // may still be running on the side stream; the hot build of this step leaves it alone.  A berg the hot build hands over
 // at step s gets lane = s + 1: the general build does its steps s and s + 1, the hot build has it back at s + 2.
@@ -103,7 +107,9 @@ template <bool RK, bool OLD_ORDER, unsigned PH, bool FAST, int K> struct HotCfg 
   static constexpr int chunk = three ? KID_HOT3_CHUNK : ((FAST && K == 2) ? KID_FLP_CHUNK : KID_CHUNK);    // staging rows per wave (>= 7: the rows the plain build parks M .. heat_density in)
   static constexpr int waves = !FAST ? KID_GENERAL_WAVES_PER_EU : (three ? 3 : KID_WAVES_PER_EU);
 };
-template <bool RK, bool OLD_ORDER, unsigned PH, bool FAST, int K = 0>
+template <bool S> __device__ __forceinline__ auto &scatter_of(Seg &seg, StageSeg &sseg) { if constexpr (S) return sseg; else return seg; }
+// STAGE: the staging instance of reproducible sums (StageSeg instead of the LDS scatter-add; launched with K = 0 only)
+template <bool RK, bool OLD_ORDER, unsigned PH, bool FAST, int K = 0, bool STAGE = false>
 __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (HotCfg<RK, OLD_ORDER, PH, FAST, K>::waves)) berg_kernel(const DevGrid *__restrict__ gtab, const kid_params *__restrict__ pp, const BergPtrs *__restrict__ bt, const long long n,
                                                    double *__restrict__ acc, const size_t ncell, const Flags fl, const Redo redo) {
   // The parameter block (142 dwords) and the 51 field pointers are read through device-memory tables on demand:
@@ -134,6 +140,7 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   const bool inrange = tid < total;
   const long long k = inrange ? (FAST ? redo.k0 + tid : (long long)redo.list[tid]) : 0ll;
   const long long kk = inrange ? k : (n - 1);
+  if constexpr (STAGE) { if (inrange) redo.st.key[k] = -1; }   // (rewritten below by a row that contributes)
   // Every load of the step is issued here, back to back, before anything is used: `alive`, the lane stamp, the cell and
   // the fields used to be three dependent round trips to HBM at the head of every wave (~15 % of its lifetime).
   const int32_t alive_v = ldg(b.i[KID_BI_ALIVE], kk);
@@ -191,6 +198,7 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
     if (grid_latlon<K>(g) && g.latref) { const long long c2 = 2ll * (mykey < 0 ? 0 : mykey); latref_s = ldg(g.latref, c2); latref_c = ldg(g.latref, c2 + 1); }
   }
   Seg seg;
+  [[maybe_unused]] StageSeg sseg{};
   if constexpr (!FAST) seg = make_runs(mykey, (lds_double *)lds_vals, (lds_int *)lds_ints, CHUNK);
   const lds_double *pk = nullptr;
   if (FAST) {
@@ -352,6 +360,8 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
 
   if (PH & (PH_THERMO | PH_SPREAD)) {
     const bool active = t.alive && !skipped;
+    if constexpr (STAGE) { sseg.val = redo.st.val; sseg.cap = redo.st.cap; sseg.row = kk; sseg.mask = 0ull; }
+    auto &sg = scatter_of<STAGE>(seg, sseg);
     if (!FAST) seg = make_runs(active ? g.idx(d.ine, d.jne) : -1, (lds_double *)lds_vals, (lds_int *)lds_ints);  // cells may have changed
     const typename CellOf<FAST>::type cellv = CellOf<FAST>::make(g, pk, d.ine, d.jne);
     // fused hot build of the plain namelist (no static bergs): every berg still active here went through the hot evolve, which
@@ -398,8 +408,8 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
       const BergThermo before = t;
       if constexpr ((PH & PH_TSPREAD) != 0) {  // thermodynamics spreads the would-be masses itself, IB:3219-3238
         const TSpreadArgs ts{d.xi, d.yj, b.orient ? b.orient[kk] : p.initial_orientation, Fl<K>::footprint(fl) != 0};
-        thermodynamics<true, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, seg, scal, &ts);
-      } else thermodynamics<false, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, seg, scal);
+        thermodynamics<true, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, sg, scal, &ts);
+      } else thermodynamics<false, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, sg, scal);
       if (active) {
         stg(b.f[KID_B_MASS], kk, t.M); stg(b.f[KID_B_THICKNESS], kk, t.T); stg(b.f[KID_B_WIDTH], kk, t.W); stg(b.f[KID_B_LENGTH], kk, t.L);
         if (t.mass_of_bits != before.mass_of_bits) stg(b.f[KID_B_MASS_OF_BITS], kk, t.mass_of_bits);
@@ -418,12 +428,13 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
     if (PH & PH_SPREAD) {  // calculate_mass_on_ocean IB:4989-5009 on the post-thermodynamics state
       const bool act2 = t.alive && !skipped;
       if ((Sw<K>::add_weight_to_ocean(p) && !Sw<K>::time_average_weight(p)) || Sw<K>::find_melt_using_spread_mass(p))
-        spread_mass<K>(g, p, cellv, t, d.uvel, d.vvel, d.ine, d.jne, d.xi, d.yj, act2, acc, ncell, seg, Fl<K>::footprint(fl) != 0,
+        spread_mass<K>(g, p, cellv, t, d.uvel, d.vvel, d.ine, d.jne, d.xi, d.yj, act2, acc, ncell, sg, Fl<K>::footprint(fl) != 0,
                        (K == 0 && b.orient) ? b.orient[kk] : p.initial_orientation);
-      if (!Fl<K>::no_diag(fl)) berg_diagnostics<K>(g, p, cellv, t, d.uvel, d.vvel, d.ine, d.jne, act2, acc, ncell, seg);
+      if (!Fl<K>::no_diag(fl)) berg_diagnostics<K>(g, p, cellv, t, d.uvel, d.vvel, d.ine, d.jne, act2, acc, ncell, sg);
     }
     if (FAST && KID_PRIO_ON) __builtin_amdgcn_s_setprio(3);   // ... and the wave that is about to retire: its slot goes to a wave that starts fetching
-    seg_flush(seg, acc, ncell);
+    if constexpr (STAGE) { if (inrange && active) { redo.st.key[kk] = g.idx(d.ine, d.jne); redo.st.mask[kk] = sseg.mask; } }
+    else seg_flush(seg, acc, ncell);
     KID_MARK("spread_done"); KID_TICK(9);
   }
 

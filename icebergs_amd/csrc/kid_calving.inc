@@ -404,7 +404,7 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   KID_HIP(h, hipStreamSynchronize(h->stream));
   const int appended = (int)(reinterpret_cast<const unsigned long long *>(h->calv_host + KID_NCALV_SCALARS)[0] & 0xffffffffull);
   if (scalars) for (int q = 0; q < KID_NCALV_SCALARS; ++q) scalars[q] = h->calv_host[q];
-  if (appended > 0) { h->tail_valid = false; if (!h->params.old_interp_flds_order) h->env_ever_stored = true; }
+  if (appended > 0) { h->tail_valid = false; h->rp.srows_n = -1; if (!h->params.old_interp_flds_order) h->env_ever_stored = true; }
   const int64_t room = h->capacity - h->n;
   if (appended > room) {
     h->n = h->capacity;

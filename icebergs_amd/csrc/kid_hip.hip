@@ -345,6 +345,11 @@ __global__ void __launch_bounds__(256) translate_list_kernel(int *list, const in
   const int total = *count;
   for (int t = blockIdx.x * 256 + threadIdx.x; t < total; t += gridDim.x * 256) list[t] = (int)inv[list[t]];
 }
+// the canonical order of reproducible sums (kid_repro.inc) through the re-binning: it orders bergs, so only its row numbers change
+__global__ void __launch_bounds__(256) translate_rows_kernel(int *rows, const unsigned *inv, long long n) {
+  const long long q = (long long)blockIdx.x * 256ll + threadIdx.x;
+  if (q < n) rows[q] = (int)inv[rows[q]];
+}
 // every field of the SoA through the permutation in ONE launch: a thread owns a destination row, reads the source row
 // number once and walks the fields (the loads of consecutive fields are independent)
 enum { KID_PERM_MAX = KID_NB_F64 + KID_NB_I32 + 2 };   // every field, the ids, the lane array of the slow-lane schedule
@@ -468,6 +473,12 @@ struct kid_handle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
   double berg_ms = 0., all_ms = 0.; int64_t berg_launches = 0;
+  // reproducible sums (kid_set_reproducible_sums, kid_repro.inc): staging table, row keys / masks, the static canonical order
+  // (valid while srows_n == n; reset wherever rows move), sort buffers, cell starts, per-cell heat and its block sums
+  bool repro = false;
+  struct Repro { double *stage = nullptr; int32_t *key = nullptr; unsigned long long *mask = nullptr; int *srows = nullptr; long long srows_n = -1;
+                 unsigned long long *k64[2] = {nullptr, nullptr}; int *rows[2] = {nullptr, nullptr}; unsigned *k32[2] = {nullptr, nullptr};
+                 int *cs = nullptr; double *cell_heat = nullptr, *part = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0; } rp;
   std::string err;
 };
 
@@ -663,6 +674,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
 }
 
 static void mts_free(kid_handle *h);
+static void repro_free(kid_handle *h);
 int kid_destroy(kid_handle *h) {
   if (!h) return KID_EINVAL;
   (void)hipSetDevice(h->device);
@@ -731,6 +743,7 @@ int kid_destroy(kid_handle *h) {
   if (h->d_fl_next) (void)hipFree(h->d_fl_next);
   if (h->d_fl_newid) (void)hipFree(h->d_fl_newid);
   mts_free(h);
+  repro_free(h);
   if (h->d_orient) (void)hipFree(h->d_orient);
   if (h->d_redo_list) (void)hipFree(h->d_redo_list);
   if (h->d_redo_count) (void)hipFree(h->d_redo_count);
@@ -932,7 +945,7 @@ int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
   if (host->n > h->capacity) { h->err = "more bergs than capacity"; return KID_ECAPACITY; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
-  h->static_rows_n = -1;   // the cached order by the static `inorder` keys belongs to the previous population
+  h->static_rows_n = -1; h->rp.srows_n = -1;   // the cached order by the static `inorder` keys belongs to the previous population
   const size_t n = (size_t)host->n;
   bool any_static = false, any_fl = false;
   for (int f = 0; f < KID_NB_F64; ++f) {
@@ -1029,6 +1042,7 @@ int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive) {
     }
     if (h->tail_valid && (int64_t)cnt < h->n) {  // a re-binning left the dead at the tail: drop them now that the count is known
       h->n = (int64_t)cnt;
+      h->rp.srows_n = -1;
       if (n_slots) *n_slots = h->n;
     }
   }
@@ -1040,7 +1054,7 @@ int kid_compact_bergs(kid_handle *h) {
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
   if (h->n == 0) return KID_OK;
-  h->static_rows_n = -1;   // rows move: the cached traversal order (mts_build_order) is of the old rows
+  h->static_rows_n = -1; h->rp.srows_n = -1;   // rows move: the cached traversal orders (mts_build_order, repro_static_order) are of the old rows
   const long long n = h->n;
   const unsigned nb = (unsigned)((n + 255) / 256);
   if (!h->d_spare_f64) {
@@ -1140,6 +1154,8 @@ int kid_move_berg_between_cells(kid_handle *h) {
 // with_lane: the lane array moves with the rows and `list` (row numbers, *list_count of them) is translated
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count) {
   h->static_rows_n = -1;   // rows move: the cached traversal order (mts_build_order) is of the old rows
+  const bool carry_repro = h->rp.srows_n == h->n;   // ... the one of reproducible sums is carried through (translate_rows_kernel)
+  h->rp.srows_n = -1;
   const long long n = h->n;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const unsigned dead_key = (unsigned)h->ncell;  // larger than any cell index
@@ -1180,6 +1196,7 @@ static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_
     KID_HIP(h, rocprim::exclusive_scan(h->d_cscan_tmp, tmp, h->d_cell_hist, h->d_cell_hist, 0u, (size_t)h->ncell + 1, rocprim::plus<unsigned>(), h->stream));
     hipLaunchKernelGGL(cell_place_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_key[0], h->d_key[1], h->d_cell_hist, h->d_idx[1], h->d_idx[0], n);
     perm = h->d_idx[1];
+    if (carry_repro) { hipLaunchKernelGGL(translate_rows_kernel, dim3(nb), dim3(256), 0, h->stream, h->rp.srows, (const unsigned *)h->d_idx[0], n); h->rp.srows_n = n; }
   }
   PermTable t{};
   int moved_f[KID_NB_F64], nmf = 0;
@@ -1263,6 +1280,16 @@ static bool fl_profile_namelist(const kid_handle *h) {
   const Flags &f = h->flags;
   return same && !h->gd.grid_is_latlon && !p.pass_fields_to_ocean_model && !f.has_static && f.has_fl && !f.footprint && !f.no_diag && !h->dbg.no_plain_build;
 }
+// the staging instance (reproducible sums): hot and general build of the general switches (K = 0), both on the main stream
+template <bool RKV, bool OLDV, unsigned PH>
+static void launch_stage(kid_handle *h, unsigned nbp, const DevGrid *gtab, const Redo &redo, long long klen) {
+  if constexpr ((PH & (PH_THERMO | PH_SPREAD)) != 0) {
+    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true, 0, true>), dim3(nbp), dim3(KID_HOT_WG), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);
+    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false, 0, true>), dim3((unsigned)std::min<long long>((klen + 63) / 64, 2048)), dim3(64), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);
+  }
+}
+static int repro_refuse(kid_handle *h);
+static int repro_fold(kid_handle *h, bool thermo, bool spread, long long k0, long long klen);
 template <unsigned PH>
 static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_len = -1) {   // range: the rows to step (default all)
   if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
@@ -1272,6 +1299,7 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
     h->err = "this entry point reads the bergs' stored environment, which kid_set_store_environment has switched off (use kid_run_step, or switch it on)";
     return KID_EINVAL;
   }
+  { const int rc_r = repro_refuse(h); if (rc_r) return rc_r; }
   hipEvent_t e0 = nullptr, e1 = nullptr;
 { int rc_t = lanes_drain(h); if (rc_t) return rc_t; }
 { int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
@@ -1286,14 +1314,17 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
   // general build leaves the critical path.  Events order a half's hot build behind its own previous general build.
   const bool plain = plain_namelist(h);   // the hot build of the default namelist carries none of the other branches
   const bool flprof = fl_profile_namelist(h);   // ... nor does the one of the footloose profile
-  const int nparts = (h->pipelined && !h->params.mts && !h->params.footloose && h->n >= 4096 && range_len < 0) ? 2 : 1;
+  constexpr bool SCATTER = (PH & (PH_THERMO | PH_SPREAD)) != 0;
+  const bool stage = SCATTER && h->repro;   // the staging instance (kid_repro.inc); one part, no pipelining
+  const int nparts = (h->pipelined && !stage && !h->params.mts && !h->params.footloose && h->n >= 4096 && range_len < 0) ? 2 : 1;
   const long long half = ((h->n / 2 + 255) / 256) * 256;
   for (int part = 0; part < nparts; ++part) {
     const long long k0 = (nparts == 1) ? range_k0 : (part == 0 ? 0 : half);
     const long long klen = (nparts == 1) ? (range_len < 0 ? h->n : range_len) : (part == 0 ? half : h->n - half);
     const unsigned nbp = (unsigned)((klen + KID_HOT_WG - 1) / KID_HOT_WG);
     const Redo redo{part == 0 ? h->d_redo_list : h->d_redo_list2, h->d_redo_cnt[part][h->redo_parity], k0, klen, nullptr, 0,
-                    h->d_fl_cursor, h->d_iceberg_counter, (long long)h->capacity, h->gd.iec - h->gd.isc + 1, h->fl_step};
+                    h->d_fl_cursor, h->d_iceberg_counter, (long long)h->capacity, h->gd.iec - h->gd.isc + 1, h->fl_step,
+                    StageTab{h->rp.stage, h->rp.key, h->rp.mask, (long long)h->capacity}};
     hipStream_t gs = (nparts == 2) ? h->side_stream : h->stream;
     if (h->evG_live[part]) KID_HIP(h, hipStreamWaitEvent(h->stream, h->evG[part], 0));
     if (nparts == 1 && h->evG_live[1]) KID_HIP(h, hipStreamWaitEvent(h->stream, h->evG[1], 0));
@@ -1304,6 +1335,12 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
     }
 #define KID_LAUNCH(RKV, OLDV)                                                                                                   \
   do {                                                                                                                          \
+    if (stage) {  /* (profiling times the hot and the general build together here) */                                        \
+      launch_stage<RKV, OLDV, PH>(h, nbp, gtab, redo, klen);                                                                    \
+      if (h->profile) { (void)hipEventRecord(e1, h->stream); h->pending.emplace_back(e0, e1); h->berg_launches++; }             \
+      h->evG_live[part] = false;                                                                                                \
+      break;                                                                                                                    \
+    }                                                                                                                           \
     if (PH == (PH_EVOLVE | PH_THERMO | PH_SPREAD) && RKV && OLDV && plain)                                                       \
       (void)kid::launch_hot_plain(h->flags.store_env ? 3 : 1, nbp, (void *)h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &redo);  \
     else if (PH == (PH_INTERP | PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD) && !RKV && !OLDV && flprof)                           \
@@ -1324,6 +1361,7 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
   if (nparts == 1) h->evG_live[1] = false;
   h->redo_prezeroed = false;
   KID_HIP(h, hipGetLastError());
+  if (stage) return repro_fold(h, (PH & PH_THERMO) != 0, (PH & (PH_SPREAD | PH_TSPREAD)) != 0, range_k0, range_len < 0 ? h->n : range_len);
   return KID_OK;
 }
 
@@ -1338,7 +1376,7 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
 // at launch; the caller alternates two blocks and launches the gather on the side stream (PipelinedStepper).
 static bool lanes_eligible(const kid_handle *h) {
   const kid_params &p = h->params;
-  return h->side_mode == 2 && h->side_stream && !p.static_icebergs && !p.mts && !p.interactive_icebergs_on &&
+  return h->side_mode == 2 && h->side_stream && !h->repro && !p.static_icebergs && !p.mts && !p.interactive_icebergs_on &&
          !p.footloose && !(p.grounding_fraction > 0.) && !p.find_melt_using_spread_mass && h->n >= 4096;
 }
 template <bool OLDV>
@@ -1425,6 +1463,7 @@ int kid_evolve_icebergs(kid_handle *h) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
   if (h->params.static_icebergs) return KID_OK;  // IB:5428
+  { const int rc_r = repro_refuse(h); if (rc_r) return rc_r; }
   if (h->params.mts) return kid_evolve_icebergs_mts(h);  // IB:5431
   if (h->params.interactive_icebergs_on) return kid_evolve_icebergs_interactive(h);
   return launch_berg<PH_EVOLVE>(h);
@@ -1492,7 +1531,9 @@ int kid_footloose_calving(kid_handle *h) {
   if (!h) return KID_EINVAL;
   if (!h->params.footloose || h->n == 0) return KID_OK;
   KID_HIP(h, hipSetDevice(h->device));
-  int rc = refresh_tables(h);
+  int rc = repro_refuse(h);
+  if (rc) return rc;
+  rc = refresh_tables(h);
   if (rc) return rc;
   h->flags.has_fl = 1;
   KID_HIP(h, hipMemsetAsync(h->d_fl_cursor, 0, sizeof(int), h->stream));
@@ -1563,6 +1604,7 @@ int kid_create_gridded_icebergs_fields(kid_handle *h) {
 
 #include "kid_mts_host.inc"
 #include "kid_calving.inc"
+#include "kid_repro.inc"
 
 int kid_step_local(kid_handle *h) {
   if (!h) return KID_EINVAL;
@@ -1571,6 +1613,8 @@ int kid_step_local(kid_handle *h) {
   h->acc_prezeroed = false;
   if (rc) return rc;
   const kid_params &p = h->params;
+  rc = repro_refuse(h);
+  if (rc) return rc;
   if (p.mts) {  // IB:5409-5512 with mts=T
     if (!h->visited) { rc = mts_first_visit(h); if (rc) return rc; }
     if (!p.static_icebergs) { rc = kid_evolve_icebergs_mts(h); if (rc) return rc; }

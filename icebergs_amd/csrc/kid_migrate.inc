@@ -242,7 +242,7 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   KID_HIP(h, hipStreamSynchronize(h->stream));
   const int nerr = (int)(*mig_pinned_word(h) & 0xffffffffull);
   h->n += m;
-  h->tail_valid = false; h->static_rows_n = -1;
+  h->tail_valid = false; h->static_rows_n = -1; h->rp.srows_n = -1;
   if (!h->params.old_interp_flds_order) h->env_ever_stored = true;
   if (nerr > 0) { h->err = "kid_unpack_immigrants: can not find a cell to place berg in! (" + std::to_string(nerr) + " bergs dropped)"; return KID_EINVAL; }
   return KID_OK;

@@ -45,6 +45,7 @@ struct Seg {
   int R;             // number of runs in this wave
   int npend;         // staged slots (wave-uniform)
   int chunk;         // staged slots per flush (KID_CHUNK; fewer in the builds that trade staging rows for a third wave per SIMD)
+  static constexpr bool stage = false;
 };
 // LDS a workgroup of `waves` waves needs for its Seg tables
 constexpr int seg_lds_doubles(int waves, int chunk = KID_CHUNK) { return waves * chunk * KID_ROW + 4; }
@@ -144,6 +145,35 @@ __device__ __forceinline__ void cell_add(double *acc, size_t ncell, int plane, i
   if (s.npend == s.chunk) seg_flush(s, acc, ncell);
 }
 
+// ---- reproducible sums (kid_set_reproducible_sums): every contribution stored, summed per cell in a fixed order --------
+// The staging instance of berg_kernel passes a StageSeg instead of a Seg: cell_add becomes a plain store of the row's value
+// into a plane-major table stage[slot * cap + row] and a bit in the row's mask, with no LDS, no atomics and no flush.  The
+// fold (kid_repro.inc) then adds, per cell and plane, the staged values of the cell's rows in the reference's traversal order
+// onto what the plane holds.  The 36 on-ocean planes are staged as their factors (nine weights, four quantities, 1/fraction
+// used) and recomputed by the fold through on_ocean_term, the expression spread_mass evaluates.
+enum : int {
+  KID_ST_W = KID_A_MASS_ON_OCEAN,    // nine spreading weights
+  KID_ST_VAR = KID_ST_W + 9,         // Mass, Area*scaling, uvel*Area*scaling, vvel*Area*scaling
+  KID_ST_IFU = KID_ST_VAR + 4,       // 1 / fraction_used
+  KID_ST_HEAT = KID_ST_IFU + 1,      // the berg's term of net_heat_to_ocean
+  KID_ST_CORE = KID_ST_HEAT + 1,     // slots without the diagnostic planes
+  KID_ST_N = KID_ST_CORE + (KID_NACC - KID_NACC_CORE)
+};
+static_assert(KID_ST_N <= 64, "one mask bit per staging slot");
+__host__ __device__ constexpr int stage_slot(int plane) { return plane < KID_A_MASS_ON_OCEAN ? plane : plane - KID_NACC_CORE + KID_ST_CORE; }
+__device__ __forceinline__ double on_ocean_term(double w, double var, double Ifu) { return w * var * Ifu; }
+struct StageSeg {
+  double *val;             // [KID_ST_N][cap]
+  long long cap, row;
+  unsigned long long mask; // bit q: slot q of this row holds a value of this launch
+  static constexpr bool stage = true;
+  __device__ __forceinline__ void put(int slot, double v) { val[(size_t)slot * (size_t)cap + (size_t)row] = v; mask |= 1ull << slot; }
+};
+__device__ __forceinline__ void cell_add(double *, size_t, int plane, int, double v, StageSeg &s, bool active) {
+  if (active) s.put(stage_slot(plane), v);
+}
+__device__ __forceinline__ void seg_flush(StageSeg &, double *, size_t) {}
+
 // one out-of-line copy of ocml's pow (about 3 KB of code per inlined call site)
 __device__ __noinline__ double kid_pow(double x, double y) { return pow(x, y); }
 // x**y for the melt laws (x >= 0, y in {0.2, 0.8}): exp(y*log(x)) is within ~2e-15 relative of the correctly rounded pow
@@ -199,17 +229,17 @@ __device__ __forceinline__ int minloc_abs10(const double *tab, double v) {  // F
 }
 
 // IB:2844-3300 thermodynamics for one berg.  Writes the new state into `b`, scatters into acc planes.
-template <int K = 0, class CELL>
+template <int K = 0, class CELL, class SEG>
 __device__ __forceinline__ void spread_mass(const DevGrid &g, const kid_params &p, const CELL &cellv, const BergThermo &b, double uvel, double vvel,
-                                            int i, int j, double x, double y, bool active, double *acc, size_t ncell, Seg &seg, bool footprint, double theta);
+                                            int i, int j, double x, double y, bool active, double *acc, size_t ncell, SEG &seg, bool footprint, double theta);
 // TSPREAD (find_melt_using_spread_mass with Iceberg_melt_without_decay, IB:3219-3238): the masses the berg WOULD have after
 // the step are spread onto the ocean from inside thermodynamics, before the berg is put back to what it was.  A compile-
 // time switch: the spreading code is inlined only into the launches of that namelist combination.
 struct TSpreadArgs { double xi, yj, theta; bool footprint; };
-template <bool TSPREAD = false, int K = 0, class CELL>
+template <bool TSPREAD = false, int K = 0, class CELL, class SEG>
 __device__ __forceinline__ void thermodynamics(const DevGrid &g, const kid_params &p, const CELL &cellv, BergThermo &b, const Env &e,
                                                double uvel, double vvel, double lat, int i, int j, bool active,
-                                               double *acc, size_t ncell, Seg &seg, double *scal, const TSpreadArgs *ts = nullptr) {
+                                               double *acc, size_t ncell, SEG &seg, double *scal, const TSpreadArgs *ts = nullptr) {
   constexpr double perday = 1. / 86400.;
   const double dt = p.dt;
   const Rcp rdt = kid_rcp(dt);   // the many x/dt below share one reciprocal (exact division with -DKID_EXACT_MATH)
@@ -354,8 +384,11 @@ __device__ __forceinline__ void thermodynamics(const DevGrid &g, const kid_param
     const double hv = ok ? melt * ms * dt : 0.;
     if (__ballot(hv != 0.) != 0ull) {   // heat_density = 0 everywhere (every BASELINE config): nothing to sum, nothing to stage
       KID_ACC(KID_A_CALVING_HFLX, melt * rarea * ms);
-      const double h = wave_sum(hv);
-      if (__lane_id() == 0 && h != 0.) unsafeAtomicAdd(scal + KID_S_NET_HEAT_TO_OCEAN, h);
+      if constexpr (SEG::stage) { if (ok) seg.put(KID_ST_HEAT, hv); }
+      else {
+        const double h = wave_sum(hv);
+        if (__lane_id() == 0 && h != 0.) unsafeAtomicAdd(scal + KID_S_NET_HEAT_TO_OCEAN, h);
+      }
     }
   }
   melt = dM * rdt; KID_ACC(KID_A_BERG_MELT, melt * rarea * ms);
@@ -538,9 +571,9 @@ __device__ __noinline__ void hexagon_into_quadrants(const kid_params &p, double 
 // ---------------------------------------------------------------------------------------------------------
 // IB:3895-4133 spread_mass_across_ocean_cells + calculate_sum_over_bergs_diagnositcs (IB:5014-5071)
 // ---------------------------------------------------------------------------------------------------------
-template <int K, class CELL>
+template <int K, class CELL, class SEG>
 __device__ __forceinline__ void spread_mass(const DevGrid &g, const kid_params &p, const CELL &cellv, const BergThermo &b, double uvel, double vvel,
-                                            int i, int j, double x, double y, bool active, double *acc, size_t ncell, Seg &seg, bool footprint, double theta) {
+                                            int i, int j, double x, double y, bool active, double *acc, size_t ncell, SEG &seg, bool footprint, double theta) {
   constexpr double rho_sw = 1035.;  // IB:3919 shadows the module's 1025
   const int c = g.idx(i, j);
   const double a_ij = cellv.area();
@@ -597,22 +630,33 @@ __device__ __forceinline__ void spread_mass(const DevGrid &g, const kid_params &
   const double Ifu = 1. / fraction_used;
   const double vars[4] = {Mass, Area * scaling, uvel * Area * scaling, vvel * Area * scaling};
   const int base[4] = {KID_A_MASS_ON_OCEAN, KID_A_AREA_ON_OCEAN, KID_A_UVEL_ON_OCEAN, KID_A_VVEL_ON_OCEAN};
+  if constexpr (SEG::stage) {   // the factors; the fold forms on_ocean_term(w[s], vars[v], Ifu) itself
+    if (ok) {
+#pragma unroll
+      for (int s = 0; s < 9; ++s) seg.put(KID_ST_W + s, w[s]);
+      seg.put(KID_ST_VAR, vars[0]);
+      if (footprint) { seg.put(KID_ST_VAR + 1, vars[1]); seg.put(KID_ST_VAR + 2, vars[2]); seg.put(KID_ST_VAR + 3, vars[3]); }
+      seg.put(KID_ST_IFU, Ifu);
+    }
+    (void)base; (void)acc; (void)ncell;
+    return;
+  }
 #pragma unroll
   for (int s = 0; s < 9; ++s) {
     // slot unused by the whole wave: skipped (the plain build stages all nine, so that the number of staged values -- and
     // with it the one place where the staging block is flushed -- is known at compile time)
     if (K != 1 && K != 3 && __ballot(ok && w[s] != 0.) == 0ull) continue;
-    cell_add(acc, ncell, base[0] + s, c, w[s] * vars[0] * Ifu, seg, ok);
+    cell_add(acc, ncell, base[0] + s, c, on_ocean_term(w[s], vars[0], Ifu), seg, ok);
     if (footprint) {  // wave-uniform: area / Uvel / Vvel footprints only when something downstream reads them
 #pragma unroll
-      for (int v = 1; v < 4; ++v) cell_add(acc, ncell, base[v] + s, c, w[s] * vars[v] * Ifu, seg, ok);
+      for (int v = 1; v < 4; ++v) cell_add(acc, ncell, base[v] + s, c, on_ocean_term(w[s], vars[v], Ifu), seg, ok);
     }
   }
 }
 
-template <int K = 0, class CELL>
+template <int K = 0, class CELL, class SEG>
 __device__ __forceinline__ void berg_diagnostics(const DevGrid &g, const kid_params &p, const CELL &cellv, const BergThermo &b, double uvel, double vvel,
-                                                 int i, int j, bool active, double *acc, size_t ncell, Seg &seg) {
+                                                 int i, int j, bool active, double *acc, size_t ncell, SEG &seg) {
   const int c = g.idx(i, j);
   const double area = cellv.area(), ms = b.mass_scaling;
   const bool ok = active && (area > 0.);

@@ -36,6 +36,7 @@ module kid_hip_mod
   public :: kid_num_traj_records, kid_profile_enable, kid_profile_get, kid_restart_count_bergs
   public :: kid_restart_read_bergs, kid_restart_read_bonds, kid_restart_write_bergs, kid_restart_write_bonds
   public :: kid_set_conglom_ids, kid_set_forcing_device, kid_set_iceberg_counter, kid_set_resort_interval
+  public :: kid_set_reproducible_sums
   public :: kid_set_side_stream, kid_set_store_environment, kid_set_stream, kid_sizeof, kid_step_prepare
   public :: kid_upload_bonds, kid_version
 
@@ -370,6 +371,11 @@ module kid_hip_mod
       type(c_ptr), value :: h
     end function
     integer(c_int) function kid_set_store_environment(h, on) bind(C, name='kid_set_store_environment')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function kid_set_reproducible_sums(h, on) bind(C, name='kid_set_reproducible_sums')   ! device side of parallel_reprod
       import :: c_int, c_ptr
       type(c_ptr), value :: h
       integer(c_int), value :: on

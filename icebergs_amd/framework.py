@@ -355,6 +355,10 @@ class Icebergs:
     def set_store_environment(self, on):
         self._check(self.lib.kid_set_store_environment(self.h, 1 if on else 0), "kid_set_store_environment")
 
+    def set_reproducible_sums(self, on):
+        """Bitwise-reproducible per-cell sums (the device side of parallel_reprod, include/kid.h); off by default."""
+        self._check(self.lib.kid_set_reproducible_sums(self.h, 1 if on else 0), "kid_set_reproducible_sums")
+
     def bergs_chksum(self):
         """(chksum, chksum2, chksum3, chksum4, chksum5, #) of bergs_chksum (FW:6889-6987), as the reference prints them"""
         out = (C.c_int64 * 6)()

@@ -98,6 +98,18 @@ int kid_set_resort_interval(kid_handle *h, int steps);
  * (kid_evolve_icebergs, kid_thermodynamics) return KID_EINVAL.  Default on. */
 int kid_set_store_environment(kid_handle *h, int on);
 
+/* Reproducible per-cell sums: the device side of the namelist's `parallel_reprod`.  Off by default.  With it on, every
+ * accumulator plane, the find_melt_using_spread_mass planes and net_heat_to_ocean are functions of the set of bergs only:
+ * each berg's contributions are stored, then summed per cell in the reference's traversal order (inorder keys start_year,
+ * start_day, start_mass, start_lon, start_lat, then the berg id) as a strict left fold onto what the plane holds; the
+ * heat total is the per-cell sums reduced by a tree of fixed shape.  Results no longer depend on the row layout, the
+ * re-binning interval, compaction, wave scheduling or fused versus phase-by-phase launches; per-berg arithmetic is that
+ * of the default path.  Turning it on allocates about 0.4 KB per berg of capacity (KID_EHIP if that fails); turning it off
+ * frees it.  Not implemented together with mts, interactive_icebergs_on or footloose: KID_EUNSUPPORTED, here and at
+ * every step while both are on (kid_last_error names the switch).  The sum across GPUs of a sharded run stays the
+ * all-reduce's. */
+int kid_set_reproducible_sums(kid_handle *h, int on);
+
 /* Forcing ingest on the device: the block of icebergs_run that builds grd%uo .. grd%hi from the
  * coupler's arguments, IB:5236-5383 + invert_tau_for_du IB:8272-8296: B/C-grid velocities, B/C/A-grid wind stress,
  * stress -> velocity difference, the Kelvin test on sst, sss = -1 when absent, land / NaN scrub.  One rank owns the
