@@ -72,9 +72,56 @@ template <int K> struct Fl {
 // Where the staging instance (STAGE = true, kid_set_reproducible_sums) puts a row's contributions (StageSeg, kid_thermo.hpp):
 // val[slot * cap + row]; key[row] = the cell it contributed to (-1: none in this launch); mask[row] = the slots it wrote.
 struct StageTab { double *val; int32_t *key; unsigned long long *mask; long long cap; };
+// The re-binning instance (REBIN = true, plain hot builds only): the launch that follows a re-binning reads row perm[k] of
+// the table `bt` and writes row k of `dst`, so that the population is not copied through memory once to reorder it and a
+// second time to step it.  `moved`: the fp64 fields the re-binning moves (a bit per field; the others are zeros in either
+// order and stay where they are).  What the step does not write itself -- xs/xd: n8 8-byte and n4 4-byte fields -- is
+// copied from the source row to the destination row at the head of the kernel.
+// `surplus`: moved fp64 fields the step does not write that found no place among the head copies (a population that carries
+// more state than config 2: *_old with periodic_reentry, the footloose members ...): copied by every row, eight at a time.
+enum { KID_RB_NX8 = 10, KID_RB_NX4 = 4 };
+struct RebinTab { BergPtrs dst; const void *xs[KID_RB_NX8 + KID_RB_NX4]; void *xd[KID_RB_NX8 + KID_RB_NX4]; int n8, n4; unsigned long long moved, surplus; };
 struct Redo { int *list; int *count; long long k0, klen; int *lane; int step;    // k0, klen: the rows the hot build covers in this launch
               int *fl_cursor; int32_t *fl_counter; long long fl_capacity; int fl_iNg; unsigned fl_step;   // PH_FL: where footloose children go (FlChildCtx)
-              StageTab st{}; };
+              StageTab st{};
+              const RebinTab *rb = nullptr; const unsigned *perm = nullptr; };   // REBIN: destination table + extras, source row of every destination row
+// the fields a plain hot build stores for a berg it steps: by the evolve, by the thermodynamics (K = 3: with the environment)
+constexpr unsigned long long rb_bit(int f) { return 1ull << f; }
+constexpr unsigned long long KID_RB_DYN = rb_bit(KID_B_LON) | rb_bit(KID_B_LAT) | rb_bit(KID_B_UVEL) | rb_bit(KID_B_VVEL) | rb_bit(KID_B_AXN) | rb_bit(KID_B_AYN) |
+                                          rb_bit(KID_B_BXN) | rb_bit(KID_B_BYN) | rb_bit(KID_B_XI) | rb_bit(KID_B_YJ);
+constexpr unsigned long long KID_RB_ENV = rb_bit(KID_B_UO) | rb_bit(KID_B_VO) | rb_bit(KID_B_UI) | rb_bit(KID_B_VI) | rb_bit(KID_B_UA) | rb_bit(KID_B_VA) |
+                                          rb_bit(KID_B_SSH_X) | rb_bit(KID_B_SSH_Y) | rb_bit(KID_B_SST) | rb_bit(KID_B_SSS) | rb_bit(KID_B_CN) | rb_bit(KID_B_HI);
+constexpr unsigned long long rb_thermo_fields(int K) {
+  return rb_bit(KID_B_MASS) | rb_bit(KID_B_THICKNESS) | rb_bit(KID_B_WIDTH) | rb_bit(KID_B_LENGTH) | rb_bit(KID_B_MASS_OF_BITS) | (K == 3 ? KID_RB_ENV : 0ull);
+}
+static_assert(KID_NB_F64 <= 64, "one bit per fp64 field");
+// The table is written by a launch of its own before the kernel starts and by nothing while it runs: read through the constant
+// address space its words are scalar loads.  (As plain global memory every pointer of it was a vector load followed by a wait
+// for everything in flight, once per field: the re-binning launch took 1.85 ms where the copy and a fresh hot build take 1.53.)
+typedef const __attribute__((address_space(4))) RebinTab cRebinTab;
+template <bool REBIN> struct DstTab { static __device__ __forceinline__ const BergPtrs &get(const BergPtrs &b, const Redo &) { return b; } };
+template <> struct DstTab<true> { static __device__ __forceinline__ const auto &get(const BergPtrs &, const Redo &r) { return ((cRebinTab *)r.rb)->dst; } };
+// A row the re-binning instance does not step (dead, handed to the general build, left the domain): the fields of `m` --
+// and the cell -- go from the source row to the destination row unchanged.  The rare path: the source row number is read
+// again, nothing is held for it across the step.
+template <class BD> __device__ __forceinline__ void rebin_copy_row(const BergPtrs &b, const BD &bd, const unsigned *perm, unsigned long long m, bool cell, long long k) {
+  const long long ks = (long long)perm[k];
+  int32_t ci = 0, cj = 0;
+  if (cell) { ci = ldg(b.i[KID_BI_INE], ks); cj = ldg(b.i[KID_BI_JNE], ks); }
+  // eight fields at a time: their loads are in flight together (one field after the other was a round trip to memory per
+  // field for a wave with a single such lane, twice the lifetime of a wave without)
+  while (m != 0ull) {  // wave-uniform
+    int f[8];
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { f[q] = (m != 0ull) ? (int)__ffsll((long long)m) - 1 : -1; m &= m - 1ull; }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = (f[q] >= 0) ? ldg(b.f[f[q]], ks) : 0.;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) if (f[q] >= 0) stg(bd.f[f[q]], k, v[q]);
+  }
+  if (cell) { stg(bd.i[KID_BI_INE], k, ci); stg(bd.i[KID_BI_JNE], k, cj); }
+}
 // lane/step ("slow lane" schedule, launch_berg_lanes): lane[k] >= step means berg k is owned by general-build launches that
 // may still be running on the side stream; the hot build of this step leaves it alone.  A berg the hot build hands over
 // at step s gets lane = s + 1: the general build does its steps s and s + 1, the hot build has it back at s + 2.
@@ -109,14 +156,17 @@ template <bool RK, bool OLD_ORDER, unsigned PH, bool FAST, int K> struct HotCfg 
 };
 template <bool S> __device__ __forceinline__ auto &scatter_of(Seg &seg, StageSeg &sseg) { if constexpr (S) return sseg; else return seg; }
 // STAGE: the staging instance of reproducible sums (StageSeg instead of the LDS scatter-add; launched with K = 0 only)
-template <bool RK, bool OLD_ORDER, unsigned PH, bool FAST, int K = 0, bool STAGE = false>
+// REBIN: the re-binning instance (RebinTab above; launched for the whole population, without lane stamps)
+template <bool RK, bool OLD_ORDER, unsigned PH, bool FAST, int K = 0, bool STAGE = false, bool REBIN = false>
 __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (HotCfg<RK, OLD_ORDER, PH, FAST, K>::waves)) berg_kernel(const DevGrid *__restrict__ gtab, const kid_params *__restrict__ pp, const BergPtrs *__restrict__ bt, const long long n,
                                                    double *__restrict__ acc, const size_t ncell, const Flags fl, const Redo redo) {
   // The parameter block (142 dwords) and the 51 field pointers are read through device-memory tables on demand:
   // as by-value kernel arguments they were all pinned in SGPRs, overflowed the scalar file and came back as
   // thousands of v_readlane spill reloads per wave.
+  static_assert(!REBIN || (FAST && RK && OLD_ORDER && !STAGE && (K == 1 || K == 3) && PH == (PH_EVOLVE | PH_THERMO | PH_SPREAD)), "the re-binning instance is a plain hot build");
   const kid_params &p = *pp;
   const BergPtrs &b = *bt;
+  const auto &bd = DstTab<REBIN>::get(b, redo);   // where the rows are stored
   const DevGrid &g = *gtab;   // like the other two tables: read on demand, not pinned in ~50 SGPRs for the whole kernel
   constexpr bool SCATTER = (PH & (PH_THERMO | PH_SPREAD)) != 0;
   constexpr int WG_WAVES = FAST ? KID_HOT_WG / 64 : 4;   // (the general build is launched one wave per workgroup; its other entry points with up to four)
@@ -141,27 +191,40 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   const long long k = inrange ? (FAST ? redo.k0 + tid : (long long)redo.list[tid]) : 0ll;
   const long long kk = inrange ? k : (n - 1);
   if constexpr (STAGE) { if (inrange) redo.st.key[k] = -1; }   // (rewritten below by a row that contributes)
+  // REBIN: kk is the destination row, ks the row it comes from; otherwise they are the same row
+  long long ks = kk;
+  [[maybe_unused]] double x8[KID_RB_NX8];
+  [[maybe_unused]] int32_t x4[KID_RB_NX4];
+  if constexpr (REBIN) {
+    ks = (long long)redo.perm[kk];
+    // what the step does not write itself: loaded first, so that it has arrived when `alive` has
+    cRebinTab &rb = *(cRebinTab *)redo.rb;
+#pragma unroll
+    for (int q = 0; q < KID_RB_NX8; ++q) x8[q] = (q < rb.n8) ? ldg((const double *)rb.xs[q], ks) : 0.;
+#pragma unroll
+    for (int q = 0; q < KID_RB_NX4; ++q) x4[q] = (q < rb.n4) ? ldg((const int32_t *)rb.xs[KID_RB_NX8 + q], ks) : 0;
+  }
   // Every load of the step is issued here, back to back, before anything is used: `alive`, the lane stamp, the cell and
   // the fields used to be three dependent round trips to HBM at the head of every wave (~15 % of its lifetime).
-  const int32_t alive_v = ldg(b.i[KID_BI_ALIVE], kk);
+  const int32_t alive_v = ldg(b.i[KID_BI_ALIVE], ks);
   // (no branch around the lane-stamp load -- the join would wait for it: without stamps it re-reads `alive`)
-  const int32_t lane_v = FAST ? ldg(redo.lane ? (const int32_t *)redo.lane : (const int32_t *)b.i[KID_BI_ALIVE], kk) : 0;
+  const int32_t lane_v = FAST ? ldg(redo.lane ? (const int32_t *)redo.lane : (const int32_t *)b.i[KID_BI_ALIVE], ks) : 0;
   BergDyn d;
-  d.ine = ldg(b.i[KID_BI_INE], kk); d.jne = ldg(b.i[KID_BI_JNE], kk);
-  d.xi = ldg(b.f[KID_B_XI], kk); d.yj = ldg(b.f[KID_B_YJ], kk);
-  d.lon = ldg(b.f[KID_B_LON], kk); d.lat = ldg(b.f[KID_B_LAT], kk);
-  d.uvel = ldg(b.f[KID_B_UVEL], kk); d.vvel = ldg(b.f[KID_B_VVEL], kk);
+  d.ine = ldg(b.i[KID_BI_INE], ks); d.jne = ldg(b.i[KID_BI_JNE], ks);
+  d.xi = ldg(b.f[KID_B_XI], ks); d.yj = ldg(b.f[KID_B_YJ], ks);
+  d.lon = ldg(b.f[KID_B_LON], ks); d.lat = ldg(b.f[KID_B_LAT], ks);
+  d.uvel = ldg(b.f[KID_B_UVEL], ks); d.vvel = ldg(b.f[KID_B_VVEL], ks);
   d.uvel_prev = 0.; d.vvel_prev = 0.;
   d.axn = 0.; d.ayn = 0.; d.bxn = 0.; d.byn = 0.;
   if (PH & PH_EVOLVE) {
-    d.axn = ldg(b.f[KID_B_AXN], kk); d.ayn = ldg(b.f[KID_B_AYN], kk);
-    if (!RK) { d.bxn = ldg(b.f[KID_B_BXN], kk); d.byn = ldg(b.f[KID_B_BYN], kk); }
+    d.axn = ldg(b.f[KID_B_AXN], ks); d.ayn = ldg(b.f[KID_B_AYN], ks);
+    if (!RK) { d.bxn = ldg(b.f[KID_B_BXN], ks); d.byn = ldg(b.f[KID_B_BYN], ks); }
   }
   BergThermo t;
-  t.M = ldg(b.f[KID_B_MASS], kk); t.T = ldg(b.f[KID_B_THICKNESS], kk); t.W = ldg(b.f[KID_B_WIDTH], kk); t.L = ldg(b.f[KID_B_LENGTH], kk);
-  t.n_bonds = Sw<K>::iceberg_bonds_on(p) ? ldg(b.i[KID_BI_N_BONDS], kk) : 0;
-  t.static_berg = Fl<K>::has_static(fl) ? ldg(b.f[KID_B_STATIC_BERG], kk) : 0.;
-  const bool halo = Fl<K>::has_static(fl) ? (ldg(b.f[KID_B_HALO_BERG], kk) >= 0.5) : false;
+  t.M = ldg(b.f[KID_B_MASS], ks); t.T = ldg(b.f[KID_B_THICKNESS], ks); t.W = ldg(b.f[KID_B_WIDTH], ks); t.L = ldg(b.f[KID_B_LENGTH], ks);
+  t.n_bonds = Sw<K>::iceberg_bonds_on(p) ? ldg(b.i[KID_BI_N_BONDS], ks) : 0;
+  t.static_berg = Fl<K>::has_static(fl) ? ldg(b.f[KID_B_STATIC_BERG], ks) : 0.;
+  const bool halo = Fl<K>::has_static(fl) ? (ldg(b.f[KID_B_HALO_BERG], ks) >= 0.5) : false;
   // The hot build of the fused RK4 step parks what only the thermodynamics needs in its wave's staging rows (idle until
   // the first cell_add) instead of holding the registers -- or re-reading HBM -- across the RK4 loop.
   constexpr bool SCATTER_ = (PH & (PH_THERMO | PH_SPREAD)) != 0;
@@ -169,17 +232,32 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   // footloose builds: what the footloose phase does not need either (bits, heat density, the bergy bits of the footloose bits)
   // stays in its LDS row until the thermodynamics asks for it
   constexpr bool LATE_PARK = PARK && (PH & PH_FL) != 0;
+  static_assert(!REBIN || PARK, "the re-binning instance reads its row at the head of the kernel only (ks); the loads further down use kk");
   double park_ms = 0., park_bits = 0., park_hd = 0., park_flk = 0., park_flbits = 0., park_flbergy = 0.;
   if constexpr (PARK) {
-    park_ms = ldg(b.f[KID_B_MASS_SCALING], kk); park_bits = ldg(b.f[KID_B_MASS_OF_BITS], kk);
-    park_hd = (PH & PH_THERMO) ? ldg(b.f[KID_B_HEAT_DENSITY], kk) : 0.;
+    park_ms = ldg(b.f[KID_B_MASS_SCALING], ks); park_bits = ldg(b.f[KID_B_MASS_OF_BITS], ks);
+    park_hd = (PH & PH_THERMO) ? ldg(b.f[KID_B_HEAT_DENSITY], ks) : 0.;
     if (Fl<K>::has_fl(fl)) {
-      park_flk = ldg(b.f[KID_B_FL_K], kk); park_flbits = ldg(b.f[KID_B_MASS_OF_FL_BITS], kk); park_flbergy = ldg(b.f[KID_B_MASS_OF_FL_BERGY_BITS], kk);
+      park_flk = ldg(b.f[KID_B_FL_K], ks); park_flbits = ldg(b.f[KID_B_MASS_OF_FL_BITS], ks); park_flbergy = ldg(b.f[KID_B_MASS_OF_FL_BERGY_BITS], ks);
     }
   }
   bool was_alive = inrange && (alive_v != 0);
   if (FAST && redo.lane) { if (was_alive && lane_v >= redo.step) was_alive = false; }
   KID_TICK(11);   // (the wait for `alive` / the lane stamp: the first round trip)
+  if constexpr (REBIN) {
+    cRebinTab &rb = *(cRebinTab *)redo.rb;
+    // (`alive` is among these: a row that dies in this step stores 0 to the same word at the end of the kernel, and a row that
+    // re-enters across the seam stores its *_old members after these.  Stores of one lane to one address stay in program
+    // order -- plain global stores, no nontemporal or reordered variant -- so the later store is the one that lasts.)
+    if (inrange) {
+#pragma unroll
+      for (int q = 0; q < KID_RB_NX8; ++q) if (q < rb.n8) stg((double *)rb.xd[q], kk, x8[q]);
+#pragma unroll
+      for (int q = 0; q < KID_RB_NX4; ++q) if (q < rb.n4) stg((int32_t *)rb.xd[KID_RB_NX8 + q], kk, x4[q]);
+      if (rb.surplus != 0ull) rebin_copy_row(b, bd, redo.perm, rb.surplus, false, kk);
+      if (!was_alive) rebin_copy_row(b, bd, redo.perm, rb.moved & (KID_RB_DYN | rb_thermo_fields(K)), true, kk);
+    }
+  }
   if (__ballot(was_alive) == 0ull) {  // wave-uniform; every other lane stays to the end (wave-level sums below)
     keep(d.ine); keep(d.jne); keep(d.xi); keep(d.yj); keep(d.lon); keep(d.lat); keep(d.uvel); keep(d.vvel); keep(d.axn); keep(d.ayn);
     keep(d.bxn); keep(d.byn); keep(t.M); keep(t.T); keep(t.W); keep(t.L); keep(t.n_bonds); keep(t.static_berg);
@@ -239,7 +317,10 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
     // more distinct cells than slots: the lanes of the cells beyond go to the general build one by one (handing over the whole
     // wave made 15 % of the population take the slow path by the end of a 16-step interval)
     if (myslot >= SLOTS) {
-      if (was_alive) { const int slot = atomicAdd(redo.count, 1); redo.list[slot] = (int)kk; if (redo.lane) redo.lane[kk] = redo.step + 1; }
+      if (was_alive) {
+        const int slot = atomicAdd(redo.count, 1); redo.list[slot] = (int)kk; if (redo.lane) redo.lane[kk] = redo.step + 1;
+        if constexpr (REBIN) rebin_copy_row(b, bd, redo.perm, ((cRebinTab *)redo.rb)->moved & (KID_RB_DYN | rb_thermo_fields(K)), true, kk);   // the general build finds it in the new arrays
+      }
       was_alive = false;
     }
     }
@@ -298,6 +379,7 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
         redo.list[slot] = (int)kk;
         if (redo.lane) redo.lane[kk] = redo.step + 1;
         skipped = true; tickets = 0u; err = 0;
+        if constexpr (REBIN) rebin_copy_row(b, bd, redo.perm, ((cRebinTab *)redo.rb)->moved & (KID_RB_DYN | rb_thermo_fields(K)), true, kk);
       } else {
         // a berg whose cell leaves the computational domain is packed-and-deleted by send_bergs_to_other_pes on a
         // PE without that neighbour (FW:3024-3041)
@@ -315,17 +397,17 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
               double xi2, yj2;
               if (!pos_within_cell<false>(g, p, cell2, d.lon, d.lat, i2, d.jne, xi2, yj2, perr, pbail)) err = 1;  // not in the cell one period away: 'can not find a cell to place berg in!' FW:3660
               d.ine = i2; d.xi = xi2; d.yj = yj2;
-              stg(b.f[KID_B_UVEL_OLD], kk, d.uvel); stg(b.f[KID_B_VVEL_OLD], kk, d.vvel); stg(b.f[KID_B_LON_OLD], kk, d.lon); stg(b.f[KID_B_LAT_OLD], kk, d.lat);
+              stg(bd.f[KID_B_UVEL_OLD], kk, d.uvel); stg(bd.f[KID_B_VVEL_OLD], kk, d.vvel); stg(bd.f[KID_B_LON_OLD], kk, d.lon); stg(bd.f[KID_B_LAT_OLD], kk, d.lat);
               back = true;
             }
           }
           if (!back) t.alive = false;
         }
-        stg(b.f[KID_B_LON], kk, d.lon); stg(b.f[KID_B_LAT], kk, d.lat); stg(b.f[KID_B_UVEL], kk, d.uvel); stg(b.f[KID_B_VVEL], kk, d.vvel);
-        stg(b.f[KID_B_AXN], kk, d.axn); stg(b.f[KID_B_AYN], kk, d.ayn); stg(b.f[KID_B_BXN], kk, d.bxn); stg(b.f[KID_B_BYN], kk, d.byn);
-        stg(b.f[KID_B_XI], kk, d.xi); stg(b.f[KID_B_YJ], kk, d.yj);
-        stg(b.i[KID_BI_INE], kk, d.ine); stg(b.i[KID_BI_JNE], kk, d.jne);
-        if (!RK) { stg(b.f[KID_B_UVEL_PREV], kk, d.uvel_prev); stg(b.f[KID_B_VVEL_PREV], kk, d.vvel_prev); }
+        stg(bd.f[KID_B_LON], kk, d.lon); stg(bd.f[KID_B_LAT], kk, d.lat); stg(bd.f[KID_B_UVEL], kk, d.uvel); stg(bd.f[KID_B_VVEL], kk, d.vvel);
+        stg(bd.f[KID_B_AXN], kk, d.axn); stg(bd.f[KID_B_AYN], kk, d.ayn); stg(bd.f[KID_B_BXN], kk, d.bxn); stg(bd.f[KID_B_BYN], kk, d.byn);
+        stg(bd.f[KID_B_XI], kk, d.xi); stg(bd.f[KID_B_YJ], kk, d.yj);
+        stg(bd.i[KID_BI_INE], kk, d.ine); stg(bd.i[KID_BI_JNE], kk, d.jne);
+        if (!RK) { stg(bd.f[KID_B_UVEL_PREV], kk, d.uvel_prev); stg(bd.f[KID_B_VVEL_PREV], kk, d.vvel_prev); }
       }
     }
     const unsigned long long bt = __ballot(tickets != 0u);
@@ -397,10 +479,10 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
       // the environment the berg carries from here on is final (the thermodynamics only reads it): stored now, not at the end
       // of the kernel -- thirteen values less to hold across the thermodynamics and the spreading
       if (env_dirty && Fl<K>::store_env(fl) && was_alive && !skipped) {
-        stg(b.f[KID_B_UO], kk, e.uo); stg(b.f[KID_B_VO], kk, e.vo); stg(b.f[KID_B_UI], kk, e.ui); stg(b.f[KID_B_VI], kk, e.vi);
-        stg(b.f[KID_B_UA], kk, e.ua); stg(b.f[KID_B_VA], kk, e.va); stg(b.f[KID_B_SSH_X], kk, e.ssh_x); stg(b.f[KID_B_SSH_Y], kk, e.ssh_y);
-        stg(b.f[KID_B_SST], kk, e.sst); stg(b.f[KID_B_SSS], kk, e.sss); stg(b.f[KID_B_CN], kk, e.cn); stg(b.f[KID_B_HI], kk, e.hi);
-        if (PH & PH_INTERP) stg(b.f[KID_B_OD], kk, e.od);
+        stg(bd.f[KID_B_UO], kk, e.uo); stg(bd.f[KID_B_VO], kk, e.vo); stg(bd.f[KID_B_UI], kk, e.ui); stg(bd.f[KID_B_VI], kk, e.vi);
+        stg(bd.f[KID_B_UA], kk, e.ua); stg(bd.f[KID_B_VA], kk, e.va); stg(bd.f[KID_B_SSH_X], kk, e.ssh_x); stg(bd.f[KID_B_SSH_Y], kk, e.ssh_y);
+        stg(bd.f[KID_B_SST], kk, e.sst); stg(bd.f[KID_B_SSS], kk, e.sss); stg(bd.f[KID_B_CN], kk, e.cn); stg(bd.f[KID_B_HI], kk, e.hi);
+        if (PH & PH_INTERP) stg(bd.f[KID_B_OD], kk, e.od);
         env_dirty = false;
       }
       KID_PHASE_FENCE();
@@ -411,16 +493,19 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
         thermodynamics<true, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, sg, scal, &ts);
       } else thermodynamics<false, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, sg, scal);
       if (active) {
-        stg(b.f[KID_B_MASS], kk, t.M); stg(b.f[KID_B_THICKNESS], kk, t.T); stg(b.f[KID_B_WIDTH], kk, t.W); stg(b.f[KID_B_LENGTH], kk, t.L);
-        if (t.mass_of_bits != before.mass_of_bits) stg(b.f[KID_B_MASS_OF_BITS], kk, t.mass_of_bits);
+        stg(bd.f[KID_B_MASS], kk, t.M); stg(bd.f[KID_B_THICKNESS], kk, t.T); stg(bd.f[KID_B_WIDTH], kk, t.W); stg(bd.f[KID_B_LENGTH], kk, t.L);
+        if (REBIN || t.mass_of_bits != before.mass_of_bits) stg(bd.f[KID_B_MASS_OF_BITS], kk, t.mass_of_bits);
         if (Fl<K>::has_fl(fl)) {
-          stg(b.f[KID_B_MASS_OF_FL_BITS], kk, t.mass_of_fl_bits); stg(b.f[KID_B_MASS_OF_FL_BERGY_BITS], kk, t.mass_of_fl_bergy_bits);
-          stg(b.f[KID_B_FL_K], kk, t.fl_k);
+          stg(bd.f[KID_B_MASS_OF_FL_BITS], kk, t.mass_of_fl_bits); stg(bd.f[KID_B_MASS_OF_FL_BERGY_BITS], kk, t.mass_of_fl_bergy_bits);
+          stg(bd.f[KID_B_FL_K], kk, t.fl_k);
           if (t.mass_scaling != before.mass_scaling) {  // converted to a footloose child (IB:3272-3289)
-            stg(b.f[KID_B_MASS_SCALING], kk, t.mass_scaling);
-            stg(b.i[KID_BI_START_YEAR], kk, t.start_year); stg(b.f[KID_B_START_DAY], kk, t.start_day);
+            stg(bd.f[KID_B_MASS_SCALING], kk, t.mass_scaling);
+            stg(bd.i[KID_BI_START_YEAR], kk, t.start_year); stg(bd.f[KID_B_START_DAY], kk, t.start_day);
           }
         }
+      }
+      if constexpr (REBIN) {  // left the domain in the evolve: its position is stored, the rest of the row comes along unchanged
+        if (was_alive && !skipped && !active) rebin_copy_row(b, bd, redo.perm, ((cRebinTab *)redo.rb)->moved & rb_thermo_fields(K), false, kk);
       }
       KID_PHASE_FENCE();
       KID_MARK("thermo_done"); KID_TICK(8);
@@ -439,12 +524,12 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   }
 
   if (was_alive && !skipped) {
-    if (!t.alive) stg(b.i[KID_BI_ALIVE], kk, 0);
+    if (!t.alive) stg(bd.i[KID_BI_ALIVE], kk, 0);
     if (env_dirty && Fl<K>::store_env(fl)) {
-      stg(b.f[KID_B_UO], kk, e.uo); stg(b.f[KID_B_VO], kk, e.vo); stg(b.f[KID_B_UI], kk, e.ui); stg(b.f[KID_B_VI], kk, e.vi);
-      stg(b.f[KID_B_UA], kk, e.ua); stg(b.f[KID_B_VA], kk, e.va); stg(b.f[KID_B_SSH_X], kk, e.ssh_x); stg(b.f[KID_B_SSH_Y], kk, e.ssh_y);
-      stg(b.f[KID_B_SST], kk, e.sst); stg(b.f[KID_B_SSS], kk, e.sss); stg(b.f[KID_B_CN], kk, e.cn); stg(b.f[KID_B_HI], kk, e.hi);
-      if (PH & PH_INTERP) stg(b.f[KID_B_OD], kk, e.od);
+      stg(bd.f[KID_B_UO], kk, e.uo); stg(bd.f[KID_B_VO], kk, e.vo); stg(bd.f[KID_B_UI], kk, e.ui); stg(bd.f[KID_B_VI], kk, e.vi);
+      stg(bd.f[KID_B_UA], kk, e.ua); stg(bd.f[KID_B_VA], kk, e.va); stg(bd.f[KID_B_SSH_X], kk, e.ssh_x); stg(bd.f[KID_B_SSH_Y], kk, e.ssh_y);
+      stg(bd.f[KID_B_SST], kk, e.sst); stg(bd.f[KID_B_SSS], kk, e.sss); stg(bd.f[KID_B_CN], kk, e.cn); stg(bd.f[KID_B_HI], kk, e.hi);
+      if (PH & PH_INTERP) stg(bd.f[KID_B_OD], kk, e.od);
     }
   }
   const unsigned long long be = __ballot(err != 0);

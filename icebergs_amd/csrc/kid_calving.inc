@@ -341,6 +341,7 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   if (!h->params.old_interp_flds_order && !h->have_forcing) { h->err = "new bergs interpolate the forcing (IB:6353): set it before kid_calving"; return KID_EINVAL; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = lanes_drain(h); if (rc) return rc; }   // new rows must start in the hot lane
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   { const int rc = refresh_tables(h); if (rc) return rc; }
   const kid_grid_desc &d = h->gd;
   const size_t n0 = (size_t)(d.iec - d.isc + 1) * (d.jec - d.jsc + 1);

@@ -178,6 +178,7 @@ __global__ void __launch_bounds__(256) footloose_kernel(const DevGrid g, const k
 // the device-side tables are rewritten by stream-ordered one-lane kernels (the new contents travel as kernel arguments):
 // no host synchronisation, unlike a copy from pageable memory
 __global__ void set_berg_table_kernel(const BergPtrs src, BergPtrs *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = src; }
+__global__ void set_rebin_table_kernel(const RebinTab src, RebinTab *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = src; }
 __global__ void set_params_kernel(const kid_params src, kid_params *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = src; }
 __global__ void set_time_kernel(int32_t year, double yearday, kid_params *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) { dst->current_year = year; dst->current_yearday = yearday; } }
 __global__ void set_grid_kernel(const DevGrid src, DevGrid *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = src; }
@@ -427,9 +428,9 @@ struct kid_handle {
   double *d_pkt[2] = {nullptr, nullptr};   // gathered cell packets of the hot build, one set per parity of the forcing records
   // A/B switches for measurements and tests, read from the environment ONCE, when the handle is created (nothing on the
   // stepping path calls getenv): KID_MTS_NO_GRAPH, KID_STABLE_RESORT, KID_NO_PLAIN_BUILD, KID_FL_UNFUSED, KID_NEW_ORDER_UNFUSED,
-  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
+  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
   // fall-back), KID_MTS_POLL_LIMIT (spins before a lane of that kernel gives up: tests of the time-out)
-  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false;
+  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false, rebin_eager = false;
                      int mts_fused_blocks_cap = 0, mts_poll_limit = 0; } dbg;
   int32_t *d_iceberg_counter = nullptr;  // grd%iceberg_counter_grd (FW:1017)
   bool fl_place_warm = false;
@@ -440,6 +441,13 @@ struct kid_handle {
   void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
   double *d_perm_spare = nullptr;
   BergPtrs bp_alt{};            // second set of field arrays: the re-binning writes all fields there in one launch, then swaps
+  // A re-binning whose permutation is known (rebin_plan) but whose copy has not run (rebin_apply): the next whole-population
+  // plain hot build takes its rows through the permutation itself (launch_berg); anything else that looks at rows, row
+  // numbers or the pointer tables runs the copy first (rebin_flush).  Nothing of this state is visible from outside.
+  bool rebin_pending = false;
+  int64_t rebin_fused_count = 0;   // re-binnings taken by that launch so far (kid_rebin_fused_count: tests, A/B runs)
+  struct RebinPlan { PermTable t{}; int moved_f[KID_NB_F64] = {}; int nmf = 0; unsigned long long moved = 0ull; const unsigned *perm = nullptr; long long n = 0; } rplan;
+  RebinTab *d_rb = nullptr;     // device table of the re-binning instance of the plain hot builds
   unsigned *d_cell_hist = nullptr; void *d_cscan_tmp = nullptr; size_t cscan_tmp_bytes = 0; bool stable_resort = false;
   int resort_interval = 16, steps_since_sort = 0;
   // multiple time stepping / DEM
@@ -618,6 +626,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   if (getenv("KID_MTS_NO_GRAPH")) h->use_graph = false;  // A/B switch for measurements
   h->dbg.stable_resort = getenv("KID_STABLE_RESORT") != nullptr; h->dbg.no_plain_build = getenv("KID_NO_PLAIN_BUILD") != nullptr;
   h->dbg.fl_unfused = getenv("KID_FL_UNFUSED") != nullptr; h->dbg.new_order_unfused = getenv("KID_NEW_ORDER_UNFUSED") != nullptr;
+  h->dbg.rebin_eager = getenv("KID_REBIN_EAGER") != nullptr;
   h->dbg.mts_always_label = getenv("KID_MTS_ALWAYS_LABEL") != nullptr; h->dbg.mts_no_fused = getenv("KID_MTS_NO_FUSED") != nullptr;
   if (const char *e = getenv("KID_MTS_FUSED_BLOCKS_CAP")) h->dbg.mts_fused_blocks_cap = atoi(e);
   if (const char *e = getenv("KID_MTS_POLL_LIMIT")) h->dbg.mts_poll_limit = atoi(e);
@@ -644,6 +653,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   KID_HIP(h, hipMalloc(&h->bp.id, (size_t)capacity * sizeof(int64_t)));
   KID_HIP(h, hipMemset(h->bp.id, 0, (size_t)capacity * sizeof(int64_t)));
   KID_HIP(h, hipMalloc(&h->d_bp, sizeof(BergPtrs)));
+  KID_HIP(h, hipMalloc(&h->d_rb, sizeof(RebinTab)));
   KID_HIP(h, hipMalloc(&h->d_params, sizeof(kid_params)));
   KID_HIP(h, hipMalloc(&h->d_grid, sizeof(DevGrid)));
   KID_HIP(h, hipMalloc(&h->d_grid2, sizeof(DevGrid)));
@@ -707,6 +717,7 @@ int kid_destroy(kid_handle *h) {
   if (h->d_scan_tmp) (void)hipFree(h->d_scan_tmp);
   if (h->d_count) (void)hipFree(h->d_count);
   if (h->d_bp) (void)hipFree(h->d_bp);
+  if (h->d_rb) (void)hipFree(h->d_rb);
   if (h->d_params) (void)hipFree(h->d_params);
   if (h->d_grid) (void)hipFree(h->d_grid);
   if (h->d_grid2) (void)hipFree(h->d_grid2);
@@ -787,6 +798,7 @@ int kid_set_params(kid_handle *h, const kid_params *params) {
   return KID_OK;
 }
 static int refresh_tables(kid_handle *h);
+static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one)
 // order the main stream behind general-build launches that are still in flight on the side stream
 static int join_side(kid_handle *h) {
   for (int q = 0; q < 2; ++q)
@@ -814,6 +826,7 @@ int kid_set_side_stream(kid_handle *h, void *s, int enable) {
   if (rc) return rc;
   KID_HIP(h, hipStreamSynchronize(h->stream));
   { const int rc_d = lanes_drain(h); if (rc_d) return rc_d; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   KID_HIP(h, hipStreamSynchronize(h->stream));
   h->evG_live[0] = h->evG_live[1] = false; h->evC_live = false;
   h->side_stream = (hipStream_t)s;
@@ -945,6 +958,7 @@ int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
   if (host->n > h->capacity) { h->err = "more bergs than capacity"; return KID_ECAPACITY; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   h->static_rows_n = -1; h->rp.srows_n = -1;   // the cached order by the static `inorder` keys belongs to the previous population
   const size_t n = (size_t)host->n;
   bool any_static = false, any_fl = false;
@@ -996,6 +1010,7 @@ int kid_download_bergs(kid_handle *h, kid_berg_soa *host) {
   if (host->n < h->n) { h->err = "host SoA too small"; return KID_EINVAL; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = join_side(h); if (rc_j) return rc_j; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   const size_t n = (size_t)h->n;
   for (int f = 0; f < KID_NB_F64; ++f)
     if (host->f64[f]) KID_HIP(h, hipMemcpyAsync(host->f64[f], h->bp.f[f], n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1024,6 +1039,7 @@ int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = join_side(h); if (rc_j) return rc_j; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   if (n_slots) *n_slots = h->n;
   if (n_alive) {
     unsigned long long cnt = 0;
@@ -1053,6 +1069,7 @@ int kid_compact_bergs(kid_handle *h) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   if (h->n == 0) return KID_OK;
   h->static_rows_n = -1; h->rp.srows_n = -1;   // rows move: the cached traversal orders (mts_build_order, repro_static_order) are of the old rows
   const long long n = h->n;
@@ -1138,21 +1155,43 @@ static bool field_never_written(const kid_handle *h, int f) {
 // Correctness never depends on it (the kernels accept any order); speed does: the hot build shares LDS cell
 // packets and atomics between the lanes of a wave that sit in the same cell.
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count);
+static int rebin_plan(kid_handle *h);
+static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);
+static bool plain_namelist(const kid_handle *h);
+static bool lanes_eligible(const kid_handle *h);
+// Is a step of this handle ONE plain hot build over the whole population (kid_step_local's last branch -> launch_berg with
+// evolve | thermo | spread)?  Only then can the copy of a re-binning wait for the step: asked when the re-binning is planned,
+// at the head of kid_step_local and by launch_berg itself.  The slow-lane schedule (it re-bins inside the step, with the
+// copy), the two-halves schedule and reproducible sums keep the eager copy; so does a decomposed run, which packs its
+// emigrants right after the re-binning.
+static bool rebin_fusable(const kid_handle *h) {
+  const kid_params &p = h->params;
+  return !h->dbg.rebin_eager && !h->repro && !h->mig_mode && !h->pipelined && h->have_forcing && p.Runge_not_Verlet && p.old_interp_flds_order &&
+         !p.static_icebergs && !p.mts && !p.interactive_icebergs_on && !p.footloose && !p.find_melt_using_spread_mass && !lanes_eligible(h) && plain_namelist(h);
+}
 int kid_move_berg_between_cells(kid_handle *h) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (re-binning twice in a row: the second one sorts the rows of the first)
   h->steps_since_sort = 0;
   if (h->n == 0) return KID_OK;
   if (h->have_bonds) { h->err = "bergs with bonds keep their rows: no re-binning while bond tables exist"; return KID_EUNSUPPORTED; }
-  const int rc = rebin_core(h, false, nullptr, nullptr);
+  int rc = rebin_plan(h);
   if (rc) return rc;
+  if (rebin_fusable(h)) h->rebin_pending = true;
+  else { rc = rebin_apply(h, false, nullptr, nullptr); if (rc) return rc; }
   // the dead sorted to the tail; they are dropped the next time the host asks for the count (no synchronisation here)
   h->tail_valid = true;
   return KID_OK;
 }
 // with_lane: the lane array moves with the rows and `list` (row numbers, *list_count of them) is translated
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count) {
+  const int rc = rebin_plan(h);
+  return rc ? rc : rebin_apply(h, with_lane, list, list_count);
+}
+// plan: the permutation (h->rplan.perm: source row of every destination row; its inverse in d_idx[0]) and the fields that move
+static int rebin_plan(kid_handle *h) {
   h->static_rows_n = -1;   // rows move: the cached traversal order (mts_build_order) is of the old rows
   const bool carry_repro = h->rp.srows_n == h->n;   // ... the one of reproducible sums is carried through (translate_rows_kernel)
   h->rp.srows_n = -1;
@@ -1198,34 +1237,80 @@ static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_
     perm = h->d_idx[1];
     if (carry_repro) { hipLaunchKernelGGL(translate_rows_kernel, dim3(nb), dim3(256), 0, h->stream, h->rp.srows, (const unsigned *)h->d_idx[0], n); h->rp.srows_n = n; }
   }
-  PermTable t{};
-  int moved_f[KID_NB_F64], nmf = 0;
+  kid_handle::RebinPlan &pl = h->rplan;
+  pl = kid_handle::RebinPlan{};
+  PermTable &t = pl.t;
   for (int f = 0; f < KID_NB_F64; ++f) {
     if (!h->uploaded_nonzero[f] && field_never_written(h, f)) continue;  // all zeros, before and after
-    t.src[t.n8] = h->bp.f[f]; t.dst[t.n8] = h->bp_alt.f[f]; ++t.n8; moved_f[nmf++] = f;
+    t.src[t.n8] = h->bp.f[f]; t.dst[t.n8] = h->bp_alt.f[f]; ++t.n8; pl.moved_f[pl.nmf++] = f; pl.moved |= 1ull << f;
   }
   t.src[t.n8] = h->bp.id; t.dst[t.n8] = h->bp_alt.id; ++t.n8;
   for (int f = 0; f < KID_NB_I32; ++f) { t.src[t.n8 + t.n4] = h->bp.i[f]; t.dst[t.n8 + t.n4] = h->bp_alt.i[f]; ++t.n4; }
-  if (with_lane) {
-    if (h->stable_resort) { h->err = "KID_STABLE_RESORT has no inverse permutation for the slow-lane re-binning"; return KID_EUNSUPPORTED; }
-    if (!h->d_lane_alt) { KID_HIP(h, hipMalloc(&h->d_lane_alt, (size_t)h->capacity * sizeof(int))); KID_HIP(h, hipMemsetAsync(h->d_lane_alt, 0, (size_t)h->capacity * sizeof(int), h->stream)); }
-    t.src[t.n8 + t.n4] = h->d_lane; t.dst[t.n8 + t.n4] = h->d_lane_alt; ++t.n4;
-  }
-  hipLaunchKernelGGL(permute_all_kernel, dim3(nb), dim3(256), 0, h->stream, t, perm, n);
-  if (with_lane) {
-    std::swap(h->d_lane, h->d_lane_alt);
-    if (list) hipLaunchKernelGGL(translate_list_kernel, dim3(64), dim3(256), 0, h->stream, list, list_count, h->d_idx[0]);
-  }
-  for (int q = 0; q < nmf; ++q) std::swap(h->bp.f[moved_f[q]], h->bp_alt.f[moved_f[q]]);
+  pl.perm = perm; pl.n = n;
+  KID_HIP(h, hipGetLastError());
+  return KID_OK;
+}
+// the planned rows change places on the host: the second set of arrays becomes the SoA; the device's pointer table follows
+static int rebin_swap(kid_handle *h) {
+  const kid_handle::RebinPlan &pl = h->rplan;
+  for (int q = 0; q < pl.nmf; ++q) std::swap(h->bp.f[pl.moved_f[q]], h->bp_alt.f[pl.moved_f[q]]);
   std::swap(h->bp.id, h->bp_alt.id);
   for (int f = 0; f < KID_NB_I32; ++f) std::swap(h->bp.i[f], h->bp_alt.i[f]);
-  KID_HIP(h, hipGetLastError());
   if (h->tables_dirty) return refresh_tables(h);
   // only the field pointers changed: one table, not four (a launch on the side stream may still be reading it)
   { const int rc = join_side(h); if (rc) return rc; }
   hipLaunchKernelGGL(set_berg_table_kernel, dim3(1), dim3(64), 0, h->stream, h->bp, h->d_bp);
   KID_HIP(h, hipGetLastError());
   return KID_OK;
+}
+// apply: ONE launch gathers every moving field into the second set of arrays
+static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count) {
+  PermTable t = h->rplan.t;
+  const long long n = h->rplan.n;
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  if (with_lane) {
+    if (h->stable_resort) { h->err = "KID_STABLE_RESORT has no inverse permutation for the slow-lane re-binning"; return KID_EUNSUPPORTED; }
+    if (!h->d_lane_alt) { KID_HIP(h, hipMalloc(&h->d_lane_alt, (size_t)h->capacity * sizeof(int))); KID_HIP(h, hipMemsetAsync(h->d_lane_alt, 0, (size_t)h->capacity * sizeof(int), h->stream)); }
+    t.src[t.n8 + t.n4] = h->d_lane; t.dst[t.n8 + t.n4] = h->d_lane_alt; ++t.n4;
+  }
+  hipLaunchKernelGGL(permute_all_kernel, dim3(nb), dim3(256), 0, h->stream, t, h->rplan.perm, n);
+  if (with_lane) {
+    std::swap(h->d_lane, h->d_lane_alt);
+    if (list) hipLaunchKernelGGL(translate_list_kernel, dim3(64), dim3(256), 0, h->stream, list, list_count, h->d_idx[0]);
+  }
+  KID_HIP(h, hipGetLastError());
+  return rebin_swap(h);
+}
+static int rebin_flush(kid_handle *h) {
+  if (!h->rebin_pending) return KID_OK;
+  h->rebin_pending = false;
+  KID_HIP(h, hipSetDevice(h->device));
+  return rebin_apply(h, false, nullptr, nullptr);
+}
+// The table of the re-binning instance of the plain hot build K for the pending plan.  The moved fields that build does not
+// write itself are head copies (KID_RB_NX8 with the id; the int32 fields always fit); what is left over is `surplus`.
+static bool rebin_table(const kid_handle *h, int K, RebinTab &tab) {
+  const kid_handle::RebinPlan &pl = h->rplan;
+  tab = RebinTab{};
+  tab.dst = h->bp;
+  for (int q = 0; q < pl.nmf; ++q) tab.dst.f[pl.moved_f[q]] = h->bp_alt.f[pl.moved_f[q]];
+  tab.dst.id = h->bp_alt.id;
+  for (int f = 0; f < KID_NB_I32; ++f) tab.dst.i[f] = h->bp_alt.i[f];
+  tab.moved = pl.moved;
+  const unsigned long long own = KID_RB_DYN | rb_thermo_fields(K);
+  for (int q = 0; q < pl.nmf; ++q) {
+    const int f = pl.moved_f[q];
+    if ((own >> f) & 1ull) continue;
+    if (tab.n8 >= KID_RB_NX8 - 1) { tab.surplus |= 1ull << f; continue; }
+    tab.xs[tab.n8] = h->bp.f[f]; tab.xd[tab.n8] = h->bp_alt.f[f]; ++tab.n8;
+  }
+  tab.xs[tab.n8] = h->bp.id; tab.xd[tab.n8] = h->bp_alt.id; ++tab.n8;
+  static_assert(KID_NB_I32 - 2 <= KID_RB_NX4, "every int32 field but the cell is a head copy");
+  for (int f = 0; f < KID_NB_I32; ++f) {
+    if (f == KID_BI_INE || f == KID_BI_JNE) continue;
+    tab.xs[KID_RB_NX8 + tab.n4] = h->bp.i[f]; tab.xd[KID_RB_NX8 + tab.n4] = h->bp_alt.i[f]; ++tab.n4;
+  }
+  return true;
 }
 int kid_set_resort_interval(kid_handle *h, int steps) {
   if (!h || steps < 0) return KID_EINVAL;
@@ -1302,6 +1387,17 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
   { const int rc_r = repro_refuse(h); if (rc_r) return rc_r; }
   hipEvent_t e0 = nullptr, e1 = nullptr;
 { int rc_t = lanes_drain(h); if (rc_t) return rc_t; }
+  // A pending re-binning: the whole-population plain hot build takes its rows through the permutation (the re-binning
+  // instance, kid_berg_kernel.hpp) and the general build that follows finds them in the new arrays; every other launch
+  // gets the rows copied first.
+  RebinTab rtab;
+  bool rebin_fused = false;
+  int rebin_rc = KID_OK;
+  if (h->rebin_pending) {
+    rebin_fused = PH == (PH_EVOLVE | PH_THERMO | PH_SPREAD) && rebin_fusable(h) && range_k0 == 0 && range_len < 0 && h->rplan.n == h->n &&
+                  rebin_table(h, h->flags.store_env ? 3 : 1, rtab);
+    if (!rebin_fused) { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  }
 { int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
   const DevGrid *gtab = h->forc_parity ? h->d_grid2 : h->d_grid;
   h->tail_valid = false;
@@ -1322,9 +1418,13 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
     const long long k0 = (nparts == 1) ? range_k0 : (part == 0 ? 0 : half);
     const long long klen = (nparts == 1) ? (range_len < 0 ? h->n : range_len) : (part == 0 ? half : h->n - half);
     const unsigned nbp = (unsigned)((klen + KID_HOT_WG - 1) / KID_HOT_WG);
-    const Redo redo{part == 0 ? h->d_redo_list : h->d_redo_list2, h->d_redo_cnt[part][h->redo_parity], k0, klen, nullptr, 0,
-                    h->d_fl_cursor, h->d_iceberg_counter, (long long)h->capacity, h->gd.iec - h->gd.isc + 1, h->fl_step,
-                    StageTab{h->rp.stage, h->rp.key, h->rp.mask, (long long)h->capacity}};
+    Redo redo{part == 0 ? h->d_redo_list : h->d_redo_list2, h->d_redo_cnt[part][h->redo_parity], k0, klen, nullptr, 0,
+              h->d_fl_cursor, h->d_iceberg_counter, (long long)h->capacity, h->gd.iec - h->gd.isc + 1, h->fl_step,
+              StageTab{h->rp.stage, h->rp.key, h->rp.mask, (long long)h->capacity}};
+    if (rebin_fused) {
+      hipLaunchKernelGGL(set_rebin_table_kernel, dim3(1), dim3(64), 0, h->stream, rtab, h->d_rb);
+      redo.rb = h->d_rb; redo.perm = h->rplan.perm;
+    }
     hipStream_t gs = (nparts == 2) ? h->side_stream : h->stream;
     if (h->evG_live[part]) KID_HIP(h, hipStreamWaitEvent(h->stream, h->evG[part], 0));
     if (nparts == 1 && h->evG_live[1]) KID_HIP(h, hipStreamWaitEvent(h->stream, h->evG[1], 0));
@@ -1342,12 +1442,17 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
       break;                                                                                                                    \
     }                                                                                                                           \
     if (PH == (PH_EVOLVE | PH_THERMO | PH_SPREAD) && RKV && OLDV && plain)                                                       \
-      (void)kid::launch_hot_plain(h->flags.store_env ? 3 : 1, nbp, (void *)h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &redo);  \
+      (void)kid::launch_hot_plain((rebin_fused ? -1 : 1) * (h->flags.store_env ? 3 : 1), nbp, (void *)h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &redo);  \
     else if (PH == (PH_INTERP | PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD) && !RKV && !OLDV && flprof)                           \
       hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true, (PH == (PH_INTERP | PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD) && !RKV && !OLDV) ? 2 : 0>), dim3(nbp), dim3(KID_HOT_WG), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);  \
     else                                                                                                                        \
     hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true>), dim3(nbp), dim3(KID_HOT_WG), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);  \
     if (h->profile) { (void)hipEventRecord(e1, h->stream); h->pending.emplace_back(e0, e1); h->berg_launches++; } /* the timed kernel is the hot build (pass 1) */ \
+    if (rebin_fused) { /* the rows are in the second set of arrays now: the general build reads them there */                  \
+      h->rebin_pending = false; redo.rb = nullptr; redo.perm = nullptr; h->rebin_fused_count++;                                 \
+      rebin_rc = rebin_swap(h);                                                                                                 \
+      if (rebin_rc) break;   /* (the table could not follow the rows: nothing more is launched on them) */                     \
+    }                                                                                                                           \
     if (nparts == 2) { (void)hipEventRecord(h->evF[part], h->stream); (void)hipStreamWaitEvent(gs, h->evF[part], 0); }          \
     hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false>), dim3((unsigned)std::min<long long>((klen + 63) / 64, 2048)), dim3(64), 0, gs, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo); \
     if (nparts == 2) { (void)hipEventRecord(h->evG[part], gs); h->evG_live[part] = true; } else h->evG_live[part] = false;      \
@@ -1360,6 +1465,7 @@ static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_le
   }
   if (nparts == 1) h->evG_live[1] = false;
   h->redo_prezeroed = false;
+  if (rebin_rc) return rebin_rc;
   KID_HIP(h, hipGetLastError());
   if (stage) return repro_fold(h, (PH & PH_THERMO) != 0, (PH & (PH_SPREAD | PH_TSPREAD)) != 0, range_k0, range_len < 0 ? h->n : range_len);
   return KID_OK;
@@ -1383,6 +1489,7 @@ template <bool OLDV>
 static int launch_berg_lanes(kid_handle *h) {
   constexpr unsigned PH = OLDV ? (PH_EVOLVE | PH_THERMO | PH_SPREAD) : (PH_INTERP | PH_EVOLVE | PH_THERMO | PH_SPREAD);
   if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (this schedule re-bins inside the step, with the copy)
   { int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
   const bool rk = h->params.Runge_not_Verlet != 0;
   const DevGrid *gtab = h->forc_parity ? h->d_grid2 : h->d_grid;
@@ -1533,6 +1640,8 @@ int kid_footloose_calving(kid_handle *h) {
   KID_HIP(h, hipSetDevice(h->device));
   int rc = repro_refuse(h);
   if (rc) return rc;
+  rc = rebin_flush(h);
+  if (rc) return rc;
   rc = refresh_tables(h);
   if (rc) return rc;
   h->flags.has_fl = 1;
@@ -1615,6 +1724,11 @@ int kid_step_local(kid_handle *h) {
   const kid_params &p = h->params;
   rc = repro_refuse(h);
   if (rc) return rc;
+  // a pending re-binning waits for the one launch that can take it (the last branch below); every other kind of step copies first
+  if (h->rebin_pending && !rebin_fusable(h)) {
+    rc = rebin_flush(h);
+    if (rc) return rc;
+  }
   if (p.mts) {  // IB:5409-5512 with mts=T
     if (!h->visited) { rc = mts_first_visit(h); if (rc) return rc; }
     if (!p.static_icebergs) { rc = kid_evolve_icebergs_mts(h); if (rc) return rc; }
@@ -1791,6 +1905,11 @@ int kid_last_redo_count(kid_handle *h, int64_t *count) {
   KID_HIP(h, hipMemcpyAsync(c, h->d_redo_count2, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   KID_HIP(h, hipStreamSynchronize(h->stream));
   *count = (int64_t)c[0 + h->redo_parity] + (h->pipelined ? (int64_t)c[2 + h->redo_parity] : 0);
+  return KID_OK;
+}
+int kid_rebin_fused_count(kid_handle *h, int64_t *count) {
+  if (!h || !count) return KID_EINVAL;
+  *count = h->rebin_fused_count;
   return KID_OK;
 }
 int kid_profile_enable(kid_handle *h, int on) {

@@ -149,6 +149,7 @@ static int pack_core(kid_handle *h, int nd, const int32_t *dir, double *const *b
   { const int rc = mig_supported(h); if (rc) return rc; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = lanes_drain(h); if (rc) return rc; }   // a berg the slow lane still owes a step has not left yet
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   if (h->n == 0) return KID_OK;
   const MigSel s{{dir[0], nd > 1 ? dir[1] : -1}, h->gd.isc, h->gd.iec, h->gd.jsc, h->gd.jec, h->flags.has_static ? 1 : 0};
   const unsigned nb = (unsigned)((h->n + 255) / 256);
@@ -208,6 +209,7 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   if (m == 0) return KID_OK;
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = lanes_drain(h); if (rc) return rc; }
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   if (h->tail_valid) { int64_t slots = 0, alive = 0; const int rc = kid_num_bergs(h, &slots, &alive); if (rc) return rc; }   // drop a dead tail first (rows waiting to be packed are not part of it)
   if (h->n + m > h->capacity) {   // dead rows of earlier leavers and melted bergs pile up between re-binnings: reclaim them before refusing
     const int rc = kid_compact_bergs(h);

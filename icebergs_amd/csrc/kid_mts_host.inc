@@ -81,6 +81,7 @@ int kid_upload_bonds(kid_handle *h, const kid_bond_soa *host) {
   if (host->n != h->n) { h->err = "kid_upload_bonds: upload the bergs first (row counts differ)"; return KID_EINVAL; }
   if (host->max_bonds < 1 || host->max_bonds > KID_MAX_BONDS) { h->err = "max_bonds out of range"; return KID_EINVAL; }
   KID_HIP(h, hipSetDevice(h->device));
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   int rc = mts_ensure(h, host->max_bonds);
   if (rc) return rc;
   const size_t n = (size_t)h->n, cap = (size_t)h->capacity;
@@ -248,6 +249,7 @@ static int mts_break_bonds(kid_handle *h, int only_if_detected) {
 int kid_set_conglom_ids(kid_handle *h) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   int rc = mts_ensure_default(h);
   if (rc) return rc;
   const long long n = h->n;
@@ -303,6 +305,7 @@ static int mts_fold_scalars(kid_handle *h);
 // what kid_evolve_icebergs_mts and kid_evolve_icebergs_interactive do before their sweeps, when there are bergs
 static int mts_prologue(kid_handle *h) {
   KID_HIP(h, hipSetDevice(h->device));
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   int rc = mts_ensure_default(h);
   if (rc) return rc;
   if (h->params.iceberg_bonds_on && !h->have_bonds) { h->err = "iceberg_bonds_on but no bonds were uploaded (kid_upload_bonds)"; return KID_EINVAL; }

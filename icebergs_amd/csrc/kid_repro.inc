@@ -269,6 +269,7 @@ extern "C" int kid_set_reproducible_sums(kid_handle *h, int on) {
   h->repro = true;
   int rc = repro_refuse(h);
   if (!rc) rc = lanes_drain(h);   // the slow-lane schedule is not used in this mode
+  if (!rc) rc = rebin_flush(h);   // nor is the re-binning instance of the hot build
   if (!rc) rc = repro_alloc(h);
   if (rc) { repro_free(h); h->repro = false; }
   return rc;

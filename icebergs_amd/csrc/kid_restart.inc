@@ -508,6 +508,7 @@ int kid_read_restart(kid_handle *h, const char *dir) {
   if (!h || !dir) return KID_EINVAL;
   if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
   KID_HIP(h, hipSetDevice(h->device));
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   const std::string base(dir), path = base + "/icebergs.res.nc";
   int64_t nfile = 0;
   if (kid_restart_count_bergs(path.c_str(), &nfile)) {

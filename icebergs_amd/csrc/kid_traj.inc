@@ -189,6 +189,7 @@ int kid_record_posn(kid_handle *h) {
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = join_side(h); if (rc) return rc; }
   if (h->n == 0) return KID_OK;
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   { const int rc = refresh_tables(h); if (rc) return rc; }
   int fields[KID_NTRAJ_VARS];
   h->traj_nf = traj_fields(h, fields);

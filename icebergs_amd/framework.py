@@ -450,6 +450,12 @@ class Icebergs:
         self._check(self.lib.kid_last_redo_count(self.h, C.byref(c)), "kid_last_redo_count")
         return c.value
 
+    def rebin_fused_count(self):
+        """re-binnings whose copy the following plain hot build took over (include/kid.h); 0 with KID_REBIN_EAGER=1"""
+        c = C.c_int64()
+        self._check(self.lib.kid_rebin_fused_count(self.h, C.byref(c)), "kid_rebin_fused_count")
+        return c.value
+
     def profile(self, on=True):
         self._check(self.lib.kid_profile_enable(self.h, 1 if on else 0), "kid_profile_enable")
 

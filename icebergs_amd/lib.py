@@ -19,7 +19,7 @@ SYMBOLS = [
     "kid_evolve_icebergs", "kid_footloose_calving", "kid_set_footloose_step", "kid_get_footloose_step", "kid_footloose_uniform", "kid_thermodynamics", "kid_create_gridded_icebergs_fields",
     "kid_set_store_environment", "kid_set_reproducible_sums", "kid_set_iceberg_counter", "kid_get_iceberg_counter", "kid_step_local", "kid_step_gather", "kid_run_step", "kid_get_accumulators", "kid_accum_device_ptr", "kid_accum_live_count",
     "kid_bind_accum_buffer", "kid_bind_spread_mass_old", "kid_profile_enable", "kid_profile_get",
-    "kid_last_redo_count", "kid_set_side_stream", "kid_step_prepare", "kid_upload_bonds", "kid_download_bonds", "kid_evolve_icebergs_mts", "kid_set_conglom_ids", "kid_evolve_icebergs_interactive",
+    "kid_last_redo_count", "kid_rebin_fused_count", "kid_set_side_stream", "kid_step_prepare", "kid_upload_bonds", "kid_download_bonds", "kid_evolve_icebergs_mts", "kid_set_conglom_ids", "kid_evolve_icebergs_interactive",
     "kid_ingest_forcing", "kid_get_forcing",
     "kid_set_calving_params", "kid_set_calving_state", "kid_get_calving_state", "kid_calving", "kid_get_calving",
     "kid_restart_write_bergs", "kid_restart_count_bergs", "kid_restart_read_bergs", "kid_restart_write_bonds", "kid_restart_read_bonds", "kid_write_restart", "kid_read_restart", "kid_bergs_chksum",
@@ -105,6 +105,8 @@ def load():
     lib.kid_step_prepare.argtypes = [H, C.POINTER(C.c_void_p)]
     lib.kid_set_side_stream.argtypes = [H, C.c_void_p, C.c_int]
     lib.kid_last_redo_count.argtypes = [H, C.POINTER(C.c_int64)]
+    if hasattr(lib, "kid_rebin_fused_count"):   # (absent from an older build loaded through KID_HIP_SO for an A/B run)
+        lib.kid_rebin_fused_count.argtypes = [H, C.POINTER(C.c_int64)]
     lib.kid_upload_bonds.argtypes = [H, C.POINTER(T.BondSoA)]
     lib.kid_download_bonds.argtypes = [H, C.POINTER(T.BondSoA)]
     lib.kid_evolve_icebergs_mts.argtypes = [H]
@@ -134,6 +136,8 @@ def load():
     lib.kid_profile_enable.argtypes = [H, C.c_int]
     lib.kid_profile_get.argtypes = [H, dp, C.POINTER(C.c_int64), dp]
     for name in SYMBOLS:
+        if name == "kid_rebin_fused_count" and not hasattr(lib, name):   # a diagnostic: an older build stays loadable for A/B runs
+            continue
         if name not in ("kid_version", "kid_last_error", "kid_sizeof", "kid_footloose_uniform"):
             getattr(lib, name).restype = C.c_int
     lib.kid_footloose_uniform.restype = C.c_double

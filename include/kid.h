@@ -283,6 +283,10 @@ int kid_bind_spread_mass_old(kid_handle *h, void *dev_ptr, int64_t count);
 int kid_profile_enable(kid_handle *h, int on);
 /* telemetry: bergs that the hot build handed to the general build in the most recent per-berg launch */
 int kid_last_redo_count(kid_handle *h, int64_t *count);
+/* Re-binnings (kid_move_berg_between_cells) since kid_create whose copy of the rows was taken over by the plain hot build of
+ * the step that followed, instead of a launch of its own.  Diagnostic: results never depend on it; KID_REBIN_EAGER=1 in the
+ * environment at kid_create keeps it at zero. */
+int kid_rebin_fused_count(kid_handle *h, int64_t *count);
 int kid_profile_get(kid_handle *h, double *berg_kernel_ms_total, int64_t *berg_kernel_launches,
                     double *all_ms_total);
 
