@@ -460,6 +460,8 @@ struct kid_handle {
   MtsDev mts_shadow{}; bool mts_shadow_valid = false;   // what d_mts holds (the table is re-uploaded only when it differs)
   int conglom_batch = 8;                                // label-propagation sweeps launched before the first convergence check (set_conglom_ids)
   void *d_mts_tmp = nullptr; size_t mts_tmp_bytes = 0;
+  unsigned long long *d_bond_words = nullptr;           // counters of kid_initialize_bonds / kid_count_bonds (kid_bond_init.inc)
+  double bond_ext[2] = {0., 0.}; bool bond_ext_valid = false;   // smallest cell extents in metres of the static grid (bond_extents)
   hipGraphExec_t sub_graph_exec = nullptr;  // the captured sub-step loop of evolve_icebergs_mts
   long long sub_graph_n = -1; int sub_graph_steps = 0; bool sub_graph_pair = false; double sub_graph_dt = 0.; hipStream_t sub_graph_stream = nullptr;
   bool use_graph = true;
@@ -888,7 +890,7 @@ int kid_set_static_grid(kid_handle *h, const double *const fields[KID_NGRID_STAT
     if (!fields[k]) { if (k == KID_G_LONC || k == KID_G_LATC) continue; h->err = "static grid field missing"; return KID_EINVAL; }
     KID_HIP(h, hipMemcpyAsync(h->d_static[k], fields[k], h->ncell * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
-  h->have_static = true;
+  h->have_static = true; h->bond_ext_valid = false;
   int rc = pack_static(h);
   if (rc) return rc;
   const double *none[KID_NFORCING] = {};
@@ -1714,6 +1716,9 @@ int kid_create_gridded_icebergs_fields(kid_handle *h) {
 #include "kid_mts_host.inc"
 #include "kid_calving.inc"
 #include "kid_repro.inc"
+}  // extern "C"
+#include "kid_bond_init.inc"
+extern "C" {
 
 int kid_step_local(kid_handle *h) {
   if (!h) return KID_EINVAL;

@@ -53,6 +53,7 @@ static void mts_free(kid_handle *h) {
   (void)hipFree(h->d_last_key); (void)hipFree(h->d_order_flag); (void)hipFree(h->d_bond_sig); h->d_last_key = nullptr; h->d_order_flag = nullptr; h->d_bond_sig = nullptr;
   h->order_n = -1; h->mts_shadow_valid = false; h->labels_stale = true;
   (void)hipFree(h->d_mts_tmp); (void)hipFree(h->d_mts);
+  if (h->d_bond_words) { (void)hipFree(h->d_bond_words); h->d_bond_words = nullptr; }
   if (h->d_static_rows) { (void)hipFree(h->d_static_rows); h->d_static_rows = nullptr; h->static_rows_n = -1; }
   h->mts_ready = false;
 }

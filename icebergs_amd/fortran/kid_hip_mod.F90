@@ -39,6 +39,7 @@ module kid_hip_mod
   public :: kid_set_reproducible_sums, kid_rebin_fused_count
   public :: kid_set_side_stream, kid_set_store_environment, kid_set_stream, kid_sizeof, kid_step_prepare
   public :: kid_upload_bonds, kid_version
+  public :: kid_initialize_bonds, kid_count_bonds
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -362,6 +363,18 @@ module kid_hip_mod
       import :: c_int, c_ptr, kid_bond_soa
       type(c_ptr), value :: h
       type(kid_bond_soa), intent(inout) :: soa
+    end function
+    integer(c_int) function kid_initialize_bonds(h, from_radii, length, nformed) bind(C, name='kid_initialize_bonds')   ! IB:356-441
+      import :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: from_radii
+      real(c_double), value :: length
+      integer(c_int64_t), intent(out) :: nformed
+    end function
+    integer(c_int) function kid_count_bonds(h, nbonds, unmatched) bind(C, name='kid_count_bonds')   ! FW:5172-5285
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), intent(out) :: nbonds, unmatched
     end function
     integer(c_int) function kid_evolve_icebergs_mts(h) bind(C, name='kid_evolve_icebergs_mts')   ! IB:5431
       import :: c_int, c_ptr

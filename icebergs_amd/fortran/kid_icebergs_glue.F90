@@ -78,6 +78,10 @@ module kid_icebergs_glue
     logical :: calving_on = .false.        ! the calving source runs on the device too (kid_glue_set_calving)
     logical :: tau_is_velocity = .false.   ! bergs%tau_is_velocity (FW:727): tauxa / tauya are winds, not stresses
     logical :: passive_mode = .false.      ! bergs%passive_mode (FW:728): nothing is returned to the coupler
+    ! bergs%manually_initialize_bonds (FW:769), ..._from_radii and length_for_manually_initialize_bonds (FW:724-725): bonds are
+    ! formed between neighbouring bergs at initialisation (kid_icebergs_init_bonds) instead of being read from a restart file
+    logical :: manually_initialize_bonds = .false., manually_initialize_bonds_from_radii = .false.
+    real(c_double) :: length_for_manually_initialize_bonds = 1000.
     integer :: resort_interval = 16, since_sort = 0   ! rows are re-binned by cell every so many steps (kid_set_resort_interval)
     real(c_double), allocatable :: f64(:,:)                    ! (capacity, KID_NB_F64): one column per member
     integer(c_int32_t), allocatable :: i32(:,:)                ! (capacity, KID_NB_I32)
@@ -438,6 +442,9 @@ contains
     dev = 0 ; if (present(device)) dev = device
     bergs%gd = gd ; bergs%par = par ; bergs%capacity = cap
     bergs%tau_is_velocity = tau_is_velocity ; bergs%passive_mode = passive_mode
+    bergs%manually_initialize_bonds = manually_initialize_bonds
+    bergs%manually_initialize_bonds_from_radii = manually_initialize_bonds_from_radii
+    bergs%length_for_manually_initialize_bonds = length_for_manually_initialize_bonds
     call kid_check(kid_create(gd, par, cap, int(dev, c_int), bergs%h), bergs%h, 'kid_create')
     do f = 1, KID_NGRID_STATIC ; pst(f) = c_loc(st(isd, jsd, f)) ; enddo
     call kid_check(kid_set_static_grid(bergs%h, pst), bergs%h, 'kid_set_static_grid')
@@ -517,13 +524,25 @@ contains
 
   !> the tail of icebergs_init once the population and its bonds are in the lists (IB:141-176): n_bonds of every berg
   !! (assign_n_bonds, FW:5226-5252), the DEM beam tests' start positions (dem_tests_init, FW:4687-4710) and the mean element
-  !! size of constant_interaction_LW (set_constant_interaction_length_and_width, FW:4641-4684); parameters go to the device
+  !! size of constant_interaction_LW (set_constant_interaction_length_and_width, FW:4641-4684); parameters go to the device.
+  !! With iceberg_bonds_on and manually_initialize_bonds the bonds are formed first (IB:153-171: initialize_iceberg_bonds,
+  !! count_bonds with its quality check): the lists go to the handle, kid_initialize_bonds bonds the neighbours there, and the
+  !! lists are rebuilt from the rows and the bond tables it wrote.
   subroutine kid_icebergs_init_bonds(g)
     type(kid_glue), intent(inout) :: g
     type(iceberg), pointer :: this
     type(bond), pointer :: b
     integer :: grdi, grdj
     real(c_double) :: minlon, maxlon, elem_sum, l_sum, w_sum
+    integer(c_int64_t) :: nformed, nbonds, unmatched
+    if (g%par%iceberg_bonds_on /= 0 .and. g%par%max_bonds > 0 .and. g%manually_initialize_bonds) then
+      call kid_glue_flatten(g)
+      call kid_check(kid_initialize_bonds(g%h, merge(1_c_int32_t, 0_c_int32_t, g%manually_initialize_bonds_from_radii), &
+                                          g%length_for_manually_initialize_bonds, nformed), g%h, 'kid_initialize_bonds')
+      call kid_check(kid_count_bonds(g%h, nbonds, unmatched), g%h, 'kid_count_bonds')
+      if (unmatched /= 0) error stop 'kid_icebergs_init_bonds: Bonds are not matching!'   ! FW:5266-5268
+      call kid_glue_unflatten(g, keep_list_order=.true.)   ! initialize_iceberg_bonds does not reorder the lists
+    endif
     maxlon = -huge(1.0_c_double) ; minlon = huge(1.0_c_double) ; elem_sum = 0. ; l_sum = 0. ; w_sum = 0.
     do grdj = g%gd%jsd, g%gd%jed ; do grdi = g%gd%isd, g%gd%ied
       this => g%list(grdi,grdj)%first
@@ -726,12 +745,17 @@ contains
 
   !> structure of arrays -> lists: the surviving rows become nodes again, inserted in order (what unpack_berg_from_buffer2 /
   !! add_new_berg_to_list do for a berg that arrives from another PE, FW:3468, 4014); bergs the step removed are gone
-  subroutine kid_glue_unflatten(g)
+  !! keep_list_order: rows are inserted from the last to the first, so that bergs with identical `inorder` keys -- each of
+  !! which goes in front of its equals -- keep the order the rows had (the order of the lists they were flattened from)
+  subroutine kid_glue_unflatten(g, keep_list_order)
     type(kid_glue), intent(inout), target :: g
+    logical, intent(in), optional :: keep_list_order
     type(kid_berg_soa) :: soa
     type(iceberg) :: vals
-    integer(c_int64_t) :: n_slots, n_alive, k
+    integer(c_int64_t) :: n_slots, n_alive, k, kk
     integer :: q
+    logical :: rev
+    rev = .false. ; if (present(keep_list_order)) rev = keep_list_order
     call kid_check(kid_num_bergs(g%h, n_slots, n_alive), g%h, 'kid_num_bergs')
     if (n_slots > g%capacity) error stop 'kid_glue_unflatten: the population outgrew the staging arrays'
     soa%n = n_slots
@@ -741,10 +765,11 @@ contains
     call kid_check(kid_download_bergs(g%h, soa), g%h, 'kid_download_bergs')
     call kid_glue_clear_lists(g)
     if (g%par%iceberg_bonds_on /= 0 .and. g%par%max_bonds > 0) then
-      call unflatten_with_bonds(g, n_slots)
+      call unflatten_with_bonds(g, n_slots, rev)
       return
     endif
-    do k = 1, n_slots
+    do kk = 1, n_slots
+      k = merge(n_slots + 1 - kk, kk, rev)
       if (g%i32(k, KID_BI_ALIVE+1) == 0) cycle
       call row_to_node(g, k, vals)
       call kid_glue_add_berg(g, vals)
@@ -753,9 +778,10 @@ contains
 
   !> nodes and their bond lists from the rows and the bond tables: a berg's slots are put back with form_a_bond from the last to
   !! the first (each goes to the head: the list comes out in slot order), then connect_all_bonds (FW:4963-5125) by id
-  subroutine unflatten_with_bonds(g, n_slots)
+  subroutine unflatten_with_bonds(g, n_slots, rev)
     type(kid_glue), intent(inout), target :: g
     integer(c_int64_t), intent(in) :: n_slots
+    logical, intent(in) :: rev
     type(kid_bond_soa) :: bs
     type(iceberg) :: vals
     type(iceberg), pointer :: node
@@ -766,7 +792,7 @@ contains
     integer(c_int64_t), allocatable, target :: oth(:,:)
     real(c_double), allocatable, target :: f64(:,:,:)
     integer(c_int64_t), allocatable :: order(:)
-    integer(c_int64_t) :: k, lo, hi, mid, want
+    integer(c_int64_t) :: k, kk, lo, hi, mid, want
     integer :: s, f, mb
     mb = g%par%max_bonds
     allocate(cnt(n_slots), brk(n_slots, mb), oth(n_slots, mb), f64(n_slots, mb, KID_NBOND_F64), nodes(n_slots), order(n_slots))
@@ -774,7 +800,8 @@ contains
     bs%count = c_loc(cnt) ; bs%other_id = c_loc(oth) ; bs%broken = c_loc(brk)
     do f = 1, KID_NBOND_F64 ; bs%f64(f) = c_loc(f64(1,1,f)) ; enddo
     call kid_check(kid_download_bonds(g%h, bs), g%h, 'kid_download_bonds')
-    do k = 1, n_slots
+    do kk = 1, n_slots
+      k = merge(n_slots + 1 - kk, kk, rev)
       if (g%i32(k, KID_BI_ALIVE+1) == 0) cycle
       call row_to_node(g, k, vals)
       call kid_glue_add_berg(g, vals, node)

@@ -333,6 +333,23 @@ class Icebergs:
         self._check(self.lib.kid_download_bonds(self.h, C.byref(self._bond_soa(bd, n))), "kid_download_bonds")
         return bd
 
+    def initialize_bonds(self, from_radii=True, length=None):
+        """initialize_iceberg_bonds (IB:356-441) on the resident bergs: bonds every pair closer than 1.25 x the sum of its radii
+        (from_radii) or than `length` metres; returns the number of bond records added (both ends counted).  include/kid.h has
+        the ordering rules."""
+        if not from_radii and length is None:
+            raise ValueError("initialize_bonds: give a length or use from_radii")
+        n = C.c_int64()
+        self._check(self.lib.kid_initialize_bonds(self.h, 1 if from_radii else 0, 0.0 if length is None else float(length), C.byref(n)),
+                    "kid_initialize_bonds")
+        return n.value
+
+    def count_bonds(self):
+        """count_bonds (FW:5172-5285): (bond records on the computational domain, records without a matching partner)"""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.kid_count_bonds(self.h, C.byref(a), C.byref(b)), "kid_count_bonds")
+        return a.value, b.value
+
     def set_conglom_ids(self):
         self._check(self.lib.kid_set_conglom_ids(self.h), "kid_set_conglom_ids")
 

@@ -244,6 +244,29 @@ int kid_upload_bonds(kid_handle *h, const kid_bond_soa *host);
 int kid_download_bonds(kid_handle *h, kid_bond_soa *host);
 int kid_evolve_icebergs_mts(kid_handle *h);
 int kid_set_conglom_ids(kid_handle *h);
+/* The bonded tail of icebergs_init (IB:153-171) with manually_initialize_bonds: initialize_iceberg_bonds IB:356-441 +
+ * connect_all_bonds + assign_n_bonds, on the resident population.  Needs iceberg_bonds_on (KID_EINVAL otherwise).
+ * from_radii != 0: manually_initialize_bonds_from_radii (r_dist < 1.25 (radius1 + radius2), radius = sqrt(length width rdenom),
+ * rdenom = 1/(2 sqrt 3) with hexagonal_icebergs, 1/4 otherwise); else r_dist < length (length_for_manually_initialize_bonds;
+ * a non-positive length forms nothing).  r_dist is the reference's: fp64, the metric of convert_from_grid_to_meters at the mean
+ * latitude, no periodic wrap of the longitude difference, correctly rounded square roots.  Every live row takes part, static
+ * bergs and halo rows included; dead rows neither bond nor are bonded.
+ * Order: a berg's new partners fill its slots in reverse traversal order (form_a_bond inserts at the head: slot 0 is the
+ * partner the traversal -- cell, then the `inorder` keys, then row -- visits last).  Bonds already on the handle stay, in their
+ * order, behind the new ones; a pair that is bonded already is skipped, so a second call changes nothing (icebergs_init calls
+ * the routine twice).  New bonds: broken = 0, every KID_NBOND_F64 member 0.  n_bonds of every live berg is set to its count.
+ * Partner rows and slots are written on the device; the host reads two counters.  Afterwards the handle is as after
+ * kid_upload_bonds: the next step runs the `Visited` block (conglomerate labels, orig_bond_length).
+ * The search is one lane per berg over a window of cells whose half-width follows from the largest threshold of the call and
+ * the smallest cell extent of the static grid (kid_bond_init.inc), never all pairs unless the window is the whole domain.
+ * If some berg would hold more than max_bonds bonds nothing is written and KID_ECAPACITY is returned (kid_last_error gives the
+ * count and the berg's id); the handle stays usable.
+ * *nformed (may be NULL): bond records added, both ends counted. */
+int kid_initialize_bonds(kid_handle *h, int32_t from_radii, double length, int64_t *nformed);
+/* count_bonds FW:5172-5285 with check_bond_quality: *nbonds = bond records of the bergs on the computational domain (the
+ * reference's count, each bond from both its ends), *unmatched = those whose partner is not resident or holds no bond back to
+ * this berg (what the reference's quality check flags).  A device reduction and one 16-byte read; either pointer may be NULL. */
+int kid_count_bonds(kid_handle *h, int64_t *nbonds, int64_t *unmatched);
 /* evolve_icebergs (IB:7081-7200) with interactive_icebergs_on under the single-time-step Verlet scheme: velocity sweep
  * with the spring/damping terms of interactive_force inside accel, then the position sweep (kid_evolve_icebergs
  * dispatches to it when interactive_icebergs_on and mts=F) */
