@@ -489,6 +489,7 @@ struct kid_handle {
   struct Repro { double *stage = nullptr; int32_t *key = nullptr; unsigned long long *mask = nullptr; int *srows = nullptr; long long srows_n = -1;
                  unsigned long long *k64[2] = {nullptr, nullptr}; int *rows[2] = {nullptr, nullptr}; unsigned *k32[2] = {nullptr, nullptr};
                  int *cs = nullptr; double *cell_heat = nullptr, *part = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0; } rp;
+  double *d_budget = nullptr, *d_budget_plane = nullptr;   // kid_budget.inc: block partials + results of the sweep; staging plane of kid_incr_mass
   std::string err;
 };
 
@@ -757,6 +758,8 @@ int kid_destroy(kid_handle *h) {
   if (h->d_fl_newid) (void)hipFree(h->d_fl_newid);
   mts_free(h);
   repro_free(h);
+  if (h->d_budget) (void)hipFree(h->d_budget);
+  if (h->d_budget_plane) (void)hipFree(h->d_budget_plane);
   if (h->d_orient) (void)hipFree(h->d_orient);
   if (h->d_redo_list) (void)hipFree(h->d_redo_list);
   if (h->d_redo_count) (void)hipFree(h->d_redo_count);
@@ -1718,6 +1721,7 @@ int kid_create_gridded_icebergs_fields(kid_handle *h) {
 #include "kid_repro.inc"
 }  // extern "C"
 #include "kid_bond_init.inc"
+#include "kid_budget.inc"
 extern "C" {
 
 int kid_step_local(kid_handle *h) {

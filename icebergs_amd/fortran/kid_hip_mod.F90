@@ -40,6 +40,7 @@ module kid_hip_mod
   public :: kid_set_side_stream, kid_set_store_environment, kid_set_stream, kid_sizeof, kid_step_prepare
   public :: kid_upload_bonds, kid_version
   public :: kid_initialize_bonds, kid_count_bonds
+  public :: kid_budget_out, kid_budget, kid_stock, kid_incr_mass
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -375,6 +376,22 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int64_t
       type(c_ptr), value :: h
       integer(c_int64_t), intent(out) :: nbonds, unmatched
+    end function
+    integer(c_int) function kid_budget(h, res) bind(C, name='kid_budget')   ! the budget block of icebergs_run, IB:5702-5727
+      import :: c_int, c_ptr, kid_budget_out
+      type(c_ptr), value :: h
+      type(kid_budget_out), intent(out) :: res
+    end function
+    integer(c_int) function kid_stock(h, idx, val) bind(C, name='kid_stock')   ! icebergs_stock_pe, IB:8102-8133
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: idx
+      real(c_double), intent(out) :: val
+    end function
+    integer(c_int) function kid_incr_mass(h, mass, on_device, ni, nj) bind(C, name='kid_incr_mass')   ! icebergs_incr_mass, IB:6046-6074
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h, mass
+      integer(c_int32_t), value :: on_device, ni, nj
     end function
     integer(c_int) function kid_evolve_icebergs_mts(h) bind(C, name='kid_evolve_icebergs_mts')   ! IB:5431
       import :: c_int, c_ptr

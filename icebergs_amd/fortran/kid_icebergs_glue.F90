@@ -28,7 +28,8 @@ module kid_icebergs_glue
   private
   public :: iceberg, bond, linked_list, kid_glue, inorder, insert_berg_into_list, kid_glue_init, kid_glue_set_calving, kid_glue_add_berg, kid_glue_count, &
             kid_glue_flatten, kid_glue_unflatten, kid_glue_clear_lists, kid_glue_end, kid_icebergs_run, kid_icebergs_init, kid_read_icebergs_nml, &
-            kid_icebergs_init_bonds, kid_icebergs_run_local, kid_icebergs_run_finish, kid_exchange_sum, row_to_node, node_to_row, form_a_bond, kid_glue_find_berg, KID_CYCLIC_GLOBAL_DOMAIN
+            kid_icebergs_init_bonds, kid_icebergs_run_local, kid_icebergs_run_finish, kid_exchange_sum, row_to_node, node_to_row, form_a_bond, kid_glue_find_berg, KID_CYCLIC_GLOBAL_DOMAIN, &
+            kid_icebergs_stock_pe, kid_icebergs_incr_mass
   !> FMS's mpp_domains flag for a zonally periodic global domain (mpp_parameter_mod), as DRV:44 passes it in dom_x_flags
   integer, parameter :: KID_CYCLIC_GLOBAL_DOMAIN = 2
 
@@ -1024,6 +1025,29 @@ contains
       if (associated(area_berg)) area_berg(:,:) = bergs%outp(i0:i1, j0:j1, KID_O_SPREAD_AREA+1)
     endif
   end subroutine kid_icebergs_run_finish
+
+  !> icebergs_stock_pe (IB:8102-8133) behind its argument list: index = KID_STOCK_WATER or KID_STOCK_HEAT (FMS's ISTOCK_WATER,
+  !! ISTOCK_HEAT); any other index leaves value = 0., the reference's `case default`.  A device reduction over the resident bergs
+  !! and the stored ice; the lists are not needed.
+  subroutine kid_icebergs_stock_pe(bergs, index, value)
+    type(kid_glue), intent(inout) :: bergs
+    integer, intent(in) :: index
+    real(c_double), intent(out) :: value
+    value = 0.
+    if (index /= KID_STOCK_WATER .and. index /= KID_STOCK_HEAT) return   ! IB:8128-8129
+    call kid_check(kid_stock(bergs%h, int(index, c_int32_t), value), bergs%h, 'kid_stock')
+  end subroutine kid_icebergs_stock_pe
+
+  !> icebergs_incr_mass (IB:6046-6074) behind its argument list, minus the FMS time_type: mass(isc:iec, jsc:jec) takes the spread
+  !! mass of the last kid_icebergs_run, when add_weight_to_ocean is on (IB:6057) and passive_mode is off (IB:6067).
+  subroutine kid_icebergs_incr_mass(bergs, mass)
+    type(kid_glue), intent(inout) :: bergs
+    real(c_double), dimension(:,:), intent(inout), target, contiguous :: mass
+    if (.not. c_associated(bergs%h)) return                ! IB:6056
+    if (bergs%par%add_weight_to_ocean == 0) return         ! IB:6057
+    if (bergs%passive_mode) return                         ! IB:6067
+    call kid_check(kid_incr_mass(bergs%h, c_loc(mass), 0_c_int32_t, int(size(mass, 1), c_int32_t), int(size(mass, 2), c_int32_t)), bergs%h, 'kid_incr_mass')
+  end subroutine kid_icebergs_incr_mass
 
   subroutine kid_glue_end(g)   ! icebergs_end
     type(kid_glue), intent(inout) :: g

@@ -382,6 +382,36 @@ class Icebergs:
         self._check(self.lib.kid_bergs_chksum(self.h, out), "kid_bergs_chksum")
         return tuple(int(v) for v in out)
 
+    # ---- budgets (icebergs_stock_pe IB:8102-8133, icebergs_incr_mass IB:6046-6074, the budget block IB:5702-5727) ----
+    def stock(self, index):
+        """icebergs_stock_pe: index = types.ENUMS['KID_STOCK_WATER'] (kg) or ['KID_STOCK_HEAT'] (J); include/kid.h has the expression"""
+        v = C.c_double()
+        self._check(self.lib.kid_stock(self.h, int(index), C.byref(v)), "kid_stock")
+        return v.value
+
+    def budget(self):
+        """the members of kid_budget_out (include/kid_types.h) as a dict: one device sweep, one 96-byte read"""
+        out = T.BudgetOut()
+        self._check(self.lib.kid_budget(self.h, C.byref(out)), "kid_budget")
+        return {name: getattr(out, name) for name, _ in T.BudgetOut._fields_}
+
+    def incr_mass(self, plane):
+        """icebergs_incr_mass: adds the spread mass of the last gather (kg m-2) to `plane` in place.  `plane` covers the
+        computational domain, shape (njc, nic): a C-contiguous float64 numpy array, or a torch tensor on the handle's device
+        (then nothing crosses the bus: the tensor's pending work is waited for, the add runs on the handle's stream and is
+        complete on return)."""
+        if isinstance(plane, np.ndarray):
+            assert plane.dtype == np.float64 and plane.flags.c_contiguous and plane.ndim == 2, "float64, C-contiguous, 2-d"
+            self._check(self.lib.kid_incr_mass(self.h, plane.ctypes.data, 0, plane.shape[1], plane.shape[0]), "kid_incr_mass")
+            return plane
+        import torch
+        assert isinstance(plane, torch.Tensor) and plane.is_cuda and plane.dtype == torch.float64 and plane.is_contiguous() and plane.dim() == 2
+        assert plane.device.index == self.device, "the tensor lives on another device than the handle"
+        torch.cuda.current_stream(plane.device).synchronize()
+        self._check(self.lib.kid_incr_mass(self.h, plane.data_ptr(), 1, plane.shape[1], plane.shape[0]), "kid_incr_mass")
+        self.sync()
+        return plane
+
     def set_footloose_step(self, step):
         """continue the child-placement sequence of a restarted run (include/kid_rng.h)"""
         self._check(self.lib.kid_set_footloose_step(self.h, int(step)), "kid_set_footloose_step")

@@ -21,6 +21,7 @@ SYMBOLS = [
     "kid_bind_accum_buffer", "kid_bind_spread_mass_old", "kid_profile_enable", "kid_profile_get",
     "kid_last_redo_count", "kid_rebin_fused_count", "kid_set_side_stream", "kid_step_prepare", "kid_upload_bonds", "kid_download_bonds", "kid_evolve_icebergs_mts", "kid_set_conglom_ids", "kid_evolve_icebergs_interactive",
     "kid_initialize_bonds", "kid_count_bonds",
+    "kid_budget", "kid_stock", "kid_incr_mass",
     "kid_ingest_forcing", "kid_get_forcing",
     "kid_set_calving_params", "kid_set_calving_state", "kid_get_calving_state", "kid_calving", "kid_get_calving",
     "kid_restart_write_bergs", "kid_restart_count_bergs", "kid_restart_read_bergs", "kid_restart_write_bonds", "kid_restart_read_bonds", "kid_write_restart", "kid_read_restart", "kid_bergs_chksum",
@@ -114,6 +115,9 @@ def load():
     lib.kid_set_conglom_ids.argtypes = [H]
     lib.kid_initialize_bonds.argtypes = [H, C.c_int32, C.c_double, C.POINTER(C.c_int64)]
     lib.kid_count_bonds.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.kid_budget.argtypes = [H, C.POINTER(T.BudgetOut)]
+    lib.kid_stock.argtypes = [H, C.c_int32, C.POINTER(C.c_double)]
+    lib.kid_incr_mass.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     lib.kid_evolve_icebergs_interactive.argtypes = [H]
     lib.kid_download_bergs.argtypes = [H, C.POINTER(T.BergSoA)]
     lib.kid_num_bergs.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

@@ -96,6 +96,10 @@ class BondSoA(C.Structure):
     _fields_ = _parse_struct(_src, "kid_bond_soa", ENUMS)
 
 
+class BudgetOut(C.Structure):
+    _fields_ = _parse_struct(_src, "kid_budget_out", ENUMS)
+
+
 BOND_F64_NAMES = [k[len("KID_BOND_"):].lower() for k, v in sorted(
     ((k, v) for k, v in ENUMS.items() if k.startswith("KID_BOND_")), key=lambda kv: kv[1])]
 BERG_F64_NAMES = [k[len("KID_B_"):].lower() for k, v in sorted(

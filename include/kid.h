@@ -272,6 +272,40 @@ int kid_count_bonds(kid_handle *h, int64_t *nbonds, int64_t *unmatched);
  * dispatches to it when interactive_icebergs_on and mts=F) */
 int kid_evolve_icebergs_interactive(kid_handle *h);
 
+/* ---- budgets: what a coupled host asks outside the step.  Device reductions over the resident state (csrc/kid_budget.inc)
+ * and one read of 96 bytes; nothing is downloaded.  Like kid_bergs_chksum they first order themselves behind the side stream
+ * and run the copy of a pending re-binning; they change neither the population nor the planes, and a step after one of them
+ * gives the bits of a step without.  Every sum is taken over the live rows whose cell lies on the computational domain (the
+ * loops of sum_mass, FW:6617-6619): halo rows, dead rows and, in a handle that has migrated, dead rows waiting to be packed
+ * do not count.
+ * The sums are trees of fixed shape, without floating-point atomics: lanes of a wave by a butterfly, the four waves of a
+ * block through LDS, the block sums by one finishing block in a fixed order.  The shape depends on the number of rows
+ * only, so two calls on the same resident state return the same bits.  With kid_set_reproducible_sums on (and none of mts,
+ * interactive_icebergs_on, footloose, where that mode refuses to step and these calls sum as by default) the rows are first
+ * put in the mode's static order with the rows that do not count behind the others, and the same tree runs over that order:
+ * the result no longer depends on the row layout, the re-binning interval or compaction.  That is invariance to the order,
+ * not the reference's serial sum; the two differ by rounding.
+ * The host sums the structs of several handles (ranks) itself, as the reference does with mpp_sum (IB:5728-5766). */
+/* The budget block of icebergs_run (IB:5702-5727), the members of kid_budget_out (include/kid_types.h). */
+int kid_budget(kid_handle *h, kid_budget_out *out);
+/* icebergs_stock_pe (IB:8102-8133).  berg_mass = sum_mass(bergs) (IB:8119, 8124): bergs, bergy bits, footloose bits and
+ * footloose bergy bits, all of them always, weighted by mass_scaling (FW:6627); stored_mass = the stored ice of the
+ * computational domain, all classes (IB:8120, 8125; 0 for a handle without calving state).
+ *   KID_STOCK_WATER: *value = stored_mass + berg_mass            (IB:8121)
+ *   KID_STOCK_HEAT:  *value = -(stored_mass + berg_mass) * HLF   (IB:8126, kid_params.HLF): the latent heat of that ice; neither
+ *                    heat_density nor grd%stored_heat enters the reference's stock (they are kid_budget's floating_heat, stored_heat)
+ * No switch of the namelist makes the reference's routine return zero.  Any other index: *value = 0 as the reference's
+ * `case default` leaves it (IB:8128-8129), and KID_EINVAL. */
+int kid_stock(kid_handle *h, int32_t index, double *value);
+/* icebergs_incr_mass (IB:6046-6074): mass(i,j) = mass(i,j) + grd%spread_mass(i,j) over the computational domain (IB:6066-6068),
+ * with the spread mass of the last gather (KID_O_SPREAD_MASS), which is in kg m-2 already (the area division is
+ * sum_up_spread_fields', IB:6077-6150): there is none here.  Without add_weight_to_ocean the call returns at once and the plane
+ * is unchanged (IB:6057).  bergs%passive_mode (IB:6067) is not a member of kid_params: the caller skips the call, as
+ * kid_icebergs_incr_mass of the Fortran glue does.  `mass` is the caller's plane (isc:iec, jsc:jec), ni x nj with the first index
+ * fastest; another shape: KID_EINVAL.  on_device: `mass` is a device address, the add is one per-cell kernel on the handle's
+ * stream and the call does not wait for it; otherwise the plane is staged through the device and the call returns when it is back. */
+int kid_incr_mass(kid_handle *h, double *mass, int32_t on_device, int32_t ni, int32_t nj);
+
 /* grd%iceberg_counter_grd (FW:1017), the per-cell counter generate_id draws berg ids from; (isd:ied,jsd:jed) int32 */
 int kid_set_iceberg_counter(kid_handle *h, const int32_t *counter);
 int kid_get_iceberg_counter(kid_handle *h, int32_t *counter);

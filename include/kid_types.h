@@ -216,6 +216,26 @@ enum {
   KID_NSCALAR = 8
 };
 
+/* ---- budgets: icebergs_stock_pe (IB:8102-8133) and the budget block of icebergs_run (IB:5702-5727) ---- */
+enum { KID_STOCK_WATER = 1, KID_STOCK_HEAT = 2 };   /* ISTOCK_WATER, ISTOCK_HEAT of FMS's stock_constants_mod (IB:8104) */
+/* What kid_budget returns: the state sums the report prints as its `end` column, under the reference's names without the
+ * `_end` (the host keeps the `start` column, IB:5840-5854), and the step scalars the handle keeps.  Every sum runs over the
+ * live bergs of the computational domain (the loops of sum_mass / sum_heat, FW:6617, 6648) or over its cells. */
+typedef struct kid_budget_out {
+  int64_t nbergs;              /* IB:5727 count_bergs(bergs): live bergs on the computational domain */
+  int64_t nbergs_melted;       /* IB:3295, since kid_create (KID_S_NBERGS_MELTED) */
+  int64_t nbergs_calved_fl;    /* IB:2634, 3275 (KID_S_NBERGS_CALVED_FL) */
+  int64_t nspeeding_tickets;   /* IB:2314 (KID_S_NSPEEDING_TICKETS) */
+  double floating_mass;        /* IB:5707 sum_mass(bergs): (mass + mass_of_bits + mass_of_fl_bits + mass_of_fl_bergy_bits) * mass_scaling, FW:6627 */
+  double icebergs_mass;        /* IB:5708 sum_mass(justbergs): mass * mass_scaling, FW:6621 */
+  double bergy_mass;           /* IB:5709 sum_mass(justbits): (mass_of_bits + mass_of_fl_bergy_bits) * mass_scaling, FW:6623 */
+  double fl_bits_mass;         /* IB:5710 sum_mass(justflbits): mass_of_fl_bits * mass_scaling, FW:6625 */
+  double floating_heat;        /* IB:5715 sum_heat(bergs): the floating_mass term * heat_density, FW:6659-6661 */
+  double stored;               /* IB:5703 sum(grd%stored_ice(isc:iec,jsc:jec,:)); 0 without calving state */
+  double stored_heat;          /* IB:5706 sum(grd%stored_heat(isc:iec,jsc:jec)); 0 without calving state */
+  double net_heat_to_ocean;    /* IB:3130, since kid_create (KID_S_NET_HEAT_TO_OCEAN) */
+} kid_budget_out;
+
 /* diagnostics that the reference guards with `id_*>0` (diag_manager ids, FW:1567-1673) */
 enum {
   KID_DIAG_MELT_BY_CLASS  = 1 << 0,  /* IB:3119 */
