@@ -472,6 +472,7 @@ struct kid_handle {
   bool traj_on = false; kid_traj_params traj_params{}; double *d_traj_f[64] = {}; double *d_traj_day = nullptr; int64_t *d_traj_id = nullptr;
   int32_t *d_traj_year = nullptr, *d_traj_nbonds = nullptr; unsigned long long *d_traj_cursor = nullptr; long long traj_capacity = 0, traj_count_bound = 0; int traj_nf = 0;
   double *d_mig_buf = nullptr; long long mig_capacity = 0; unsigned long long *mig_word = nullptr;   // pinned staging of kid_pack_emigrants / kid_unpack_immigrants
+  double *halo_buf = nullptr; long long halo_capacity = 0;   // pinned staging of kid_pack_halo_pair / kid_unpack_halo_pair (kid_halo.inc)
   double *d_btraj_f[16] = {}; int64_t *d_btraj_id[2] = {}; int32_t *d_btraj_i[2] = {}; long long btraj_capacity = 0, btraj_count_bound = 0;   // bond samples
   double *d_spread_mass_old = nullptr;   // grd%spread_mass_old (find_melt_using_spread_mass, IB:5495-5497) + spread_mass_tmp; the handle's own or the caller's (kid_bind_spread_mass_old)
   double *d_spread_mass_old_own = nullptr;
@@ -738,6 +739,7 @@ int kid_destroy(kid_handle *h) {
   if (h->d_traj_cursor) (void)hipFree(h->d_traj_cursor);
   if (h->d_mig_buf) (void)hipHostFree(h->d_mig_buf);
   if (h->mig_word) (void)hipHostFree(h->mig_word);
+  if (h->halo_buf) (void)hipHostFree(h->halo_buf);
   for (auto &q : h->d_btraj_f) if (q) (void)hipFree(q);
   for (int f = 0; f < 2; ++f) { if (h->d_btraj_id[f]) (void)hipFree(h->d_btraj_id[f]); if (h->d_btraj_i[f]) (void)hipFree(h->d_btraj_i[f]); }
   if (h->evR) (void)hipEventDestroy(h->evR);
@@ -1950,4 +1952,5 @@ int kid_profile_get(kid_handle *h, double *berg_ms, int64_t *launches, double *a
 #include "kid_restart.inc"
 #include "kid_traj.inc"
 #include "kid_migrate.inc"
+#include "kid_halo.inc"
 #include "kid_chksum.inc"

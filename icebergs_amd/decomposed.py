@@ -10,6 +10,14 @@ several nodes.
 The tile only needs `pack_pair(axis)` -> (records for the east/north neighbour, records for the west/south neighbour) and
 `unpack_pair(from_west_or_south, from_east_or_north)`: `HipTile` wraps an `Icebergs` handle; the CPU tests plug the oracle
 in the same way.
+
+The second exchange of a step is the halo update of the on-ocean planes before the 9-point gather (mpp_update_domains in
+sum_up_spread_fields, IB:6106-6107): `TileExchange.update_halos`, with fixed-size messages, east/west then north/south so that
+a diagonal neighbour's corner arrives in two hops.  `TileExchange.step` is one step of icebergs_run for a tile with both
+exchanges in their places; for it the tile also offers the phases (`zero_accumulators`, `interp`, `evolve`, `thermodynamics`,
+`calculate_mass_on_ocean`, `gather`), its `params`, and `halo_buffer_count(axis, width)`, `pack_halo_pair(axis, width, sides)`
+-> (strip for the east/north neighbour, strip for the west/south one; None where `sides` says there is no neighbour) and
+`unpack_halo_pair(axis, from_lo, from_hi, width)`.
 """
 import numpy as np
 import torch
@@ -18,10 +26,53 @@ WIDTH = 34  # buffer_width without bonds, FW:21
 
 
 class HipTile:
-    """the migration calls of one handle (kid_pack_emigrants_pair / kid_unpack_immigrants_pair)"""
+    """the migration calls of one handle (kid_pack_emigrants_pair / kid_unpack_immigrants_pair), its halo calls
+    (kid_pack_halo_pair / kid_unpack_halo_pair, host buffers: the messages of TileExchange leave from the host, as the berg
+    records do) and the phases of a step"""
 
     def __init__(self, icebergs):
         self.ib = icebergs
+        self._halo_out = {}
+
+    @property
+    def params(self):
+        return self.ib.params
+
+    def _call(self, name):
+        self.ib._check(getattr(self.ib.lib, name)(self.ib.h), name)
+
+    def zero_accumulators(self):
+        self._call("kid_zero_accumulators")
+
+    def interp(self):
+        self._call("kid_interp_gridded_fields_to_bergs")
+
+    def evolve(self):
+        self._call("kid_evolve_icebergs")
+
+    def thermodynamics(self):
+        self._call("kid_thermodynamics")
+
+    def calculate_mass_on_ocean(self):
+        self.ib.calculate_mass_on_ocean()
+
+    def gather(self):
+        self.ib.step_gather()
+
+    def halo_buffer_count(self, axis, width=1):
+        return self.ib.halo_buffer_count(axis, width)
+
+    def pack_halo_pair(self, axis, width=1, sides=(True, True)):
+        count = self.halo_buffer_count(axis, width)
+        if (axis, count) not in self._halo_out:       # the send buffers are kept: a step packs the same sizes every time
+            self._halo_out[(axis, count)] = (np.empty(count), np.empty(count))
+        out = tuple(b if on else None for b, on in zip(self._halo_out[(axis, count)], sides))
+        if out[0] is None and out[1] is None:
+            return out
+        return self.ib.pack_halo_pair(axis, width, out=out)
+
+    def unpack_halo_pair(self, axis, from_lo, from_hi, width=1):
+        self.ib.unpack_halo_pair(axis, from_lo, from_hi, width)
 
     def pack_pair(self, axis):
         return self.ib.pack_emigrants_pair(axis)
@@ -123,3 +174,61 @@ class TileExchange:
             from_lo, from_hi = self._swap(to_hi, hi, to_lo, lo)
             if len(from_lo) or len(from_hi):
                 tile.unpack_pair(from_lo, from_hi)            # from the west / south first, FW:3064, 3160
+
+    def _swap_halo(self, to_hi, hi, to_lo, lo, count):
+        """the strips of one axis (numpy, `count` doubles each): `to_hi` to rank `hi`, `to_lo` to rank `lo`; returns
+        (from_lo, from_hi), None where there is no neighbour.  Both sides know `count`, so there is no count message."""
+        dist = self.dist
+        if hi is None and lo is None:
+            return None, None
+        if hi == lo:
+            # two tiles across a cyclic direction: one message each way, the strip sent east first.  What the peer sent east
+            # arrives here from the west, and the other way round.
+            mine = torch.from_numpy(np.concatenate([to_hi, to_lo])).to(self.device)
+            theirs = torch.empty(2 * count, dtype=torch.float64, device=self.device)
+            for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, mine, hi), dist.P2POp(dist.irecv, theirs, hi)]):
+                w.wait()
+            theirs = theirs.cpu().numpy()
+            return theirs[:count].copy(), theirs[count:].copy()
+        ops, keep, got = [], [], {}
+        for peer, strip in ((hi, to_hi), (lo, to_lo)):
+            if peer is None:
+                continue
+            t = torch.from_numpy(strip).to(self.device)
+            got[peer] = torch.empty(count, dtype=torch.float64, device=self.device)
+            keep.append(t)
+            ops += [dist.P2POp(dist.isend, t, peer), dist.P2POp(dist.irecv, got[peer], peer)]
+        for w in dist.batch_isend_irecv(ops):
+            w.wait()
+        return (got[lo].cpu().numpy() if lo is not None else None), (got[hi].cpu().numpy() if hi is not None else None)
+
+    def update_halos(self, tile, width=1):
+        """mpp_update_domains(var_on_ocean) of sum_up_spread_fields (IB:6106-6107) for this rank's tile: call it between
+        calculate_mass_on_ocean and the gather.  East/west over the computational rows, then north/south over the columns
+        isc-width .. iec+width, which carry the corners the first pass has filled."""
+        for axis, (dx, dy) in enumerate(((1, 0), (0, 1))):
+            hi, lo = self.neighbour(dx, dy), self.neighbour(-dx, -dy)
+            if hi is None and lo is None:
+                continue
+            count = tile.halo_buffer_count(axis, width)
+            to_hi, to_lo = tile.pack_halo_pair(axis, width, (hi is not None, lo is not None))
+            from_lo, from_hi = self._swap_halo(to_hi, hi, to_lo, lo, count)
+            tile.unpack_halo_pair(axis, from_lo, from_hi, width)
+
+    def step(self, tile, width=1):
+        """one step of icebergs_run for this rank's tile in the reference's order (IB:5125-5512): both exchanges in place"""
+        p = tile.params
+        for switch in ("find_melt_using_spread_mass", "mts", "interactive_icebergs_on", "footloose"):
+            if getattr(p, switch):
+                raise ValueError("TileExchange.step does not cover %s on tiles (DESIGN 7.5, out of scope)" % switch)
+        tile.zero_accumulators()                 # IB:5125-5156
+        if not p.old_interp_flds_order:
+            tile.interp()                        # IB:5423
+        tile.evolve()                            # IB:5433
+        self.exchange(tile)                      # IB:5447
+        if not p.old_interp_flds_order:
+            tile.interp()                        # IB:5473
+        tile.thermodynamics()                    # IB:5505
+        tile.calculate_mass_on_ocean()           # IB:5512 -> IB:4984
+        self.update_halos(tile, width)           # IB:6106-6107
+        tile.gather()                            # IB:6126-6150, 3419-3488

@@ -41,6 +41,7 @@ module kid_hip_mod
   public :: kid_upload_bonds, kid_version
   public :: kid_initialize_bonds, kid_count_bonds
   public :: kid_budget_out, kid_budget, kid_stock, kid_incr_mass
+  public :: kid_calculate_mass_on_ocean, kid_halo_plane_count, kid_halo_buffer_count, kid_pack_halo_pair, kid_unpack_halo_pair
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -392,6 +393,34 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int32_t
       type(c_ptr), value :: h, mass
       integer(c_int32_t), value :: on_device, ni, nj
+    end function
+    ! the halo update of the on-ocean planes of a decomposed run (mpp_update_domains in sum_up_spread_fields, IB:6106-6107);
+    ! include/kid.h has the buffer layout.  Buffers are c_ptr: c_loc of a host array (on_device = 0) or a device address (1);
+    ! c_null_ptr where there is no neighbour (NULL_PE)
+    integer(c_int) function kid_calculate_mass_on_ocean(h) bind(C, name='kid_calculate_mass_on_ocean')   ! IB:4984, no gather
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function kid_halo_plane_count(h, nplanes) bind(C, name='kid_halo_plane_count')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), intent(out) :: nplanes
+    end function
+    integer(c_int) function kid_halo_buffer_count(h, axis, width, count) bind(C, name='kid_halo_buffer_count')
+      import :: c_int, c_ptr, c_int32_t, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: axis, width
+      integer(c_int64_t), intent(out) :: count        ! doubles per direction
+    end function
+    integer(c_int) function kid_pack_halo_pair(h, axis, width, buf_hi, buf_lo, on_device) bind(C, name='kid_pack_halo_pair')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h, buf_hi, buf_lo          ! for the east / north and the west / south neighbour
+      integer(c_int32_t), value :: axis, width, on_device
+    end function
+    integer(c_int) function kid_unpack_halo_pair(h, axis, width, from_lo, from_hi, on_device) bind(C, name='kid_unpack_halo_pair')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h, from_lo, from_hi        ! what the west / south and the east / north neighbour packed
+      integer(c_int32_t), value :: axis, width, on_device
     end function
     integer(c_int) function kid_evolve_icebergs_mts(h) bind(C, name='kid_evolve_icebergs_mts')   ! IB:5431
       import :: c_int, c_ptr

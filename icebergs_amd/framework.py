@@ -213,6 +213,77 @@ class Icebergs:
         if buf.size:
             self._check(self.lib.kid_unpack_immigrants(self.h, _dp(buf), buf.shape[0]), "kid_unpack_immigrants")
 
+    # ---- halo update of the on-ocean planes of a decomposed domain (mpp_update_domains in sum_up_spread_fields, IB:6106-6107) ----
+    def calculate_mass_on_ocean(self):
+        """the spreading half of kid_create_gridded_icebergs_fields (no gather); step_gather is the other half"""
+        self._check(self.lib.kid_calculate_mass_on_ocean(self.h), "kid_calculate_mass_on_ocean")
+
+    def halo_plane_count(self):
+        n = C.c_int32()
+        self._check(self.lib.kid_halo_plane_count(self.h, C.byref(n)), "kid_halo_plane_count")
+        return n.value
+
+    def halo_buffer_count(self, axis, width=1):
+        """doubles per direction of pack_halo_pair / unpack_halo_pair (include/kid.h has the layout)"""
+        n = C.c_int64()
+        self._check(self.lib.kid_halo_buffer_count(self.h, int(axis), int(width), C.byref(n)), "kid_halo_buffer_count")
+        return n.value
+
+    def _halo_buffers(self, bufs, count, what):
+        """addresses of a (hi, lo) / (lo, hi) pair of flat float64 buffers: numpy arrays, or torch tensors on the handle's device
+        (on_device = 1); None stands for a missing side"""
+        ptrs, dev = [], None
+        for b in bufs:
+            if b is None:
+                ptrs.append(None)
+                continue
+            on_dev = not isinstance(b, np.ndarray)
+            assert dev is None or dev == on_dev, what + ": both buffers on the host or both on the device"
+            dev = on_dev
+            if on_dev:
+                import torch
+                assert isinstance(b, torch.Tensor) and b.is_cuda and b.device.index == self.device and b.dtype == torch.float64 and b.is_contiguous(), what
+                assert b.numel() == count, (what, b.numel(), count)
+                ptrs.append(b.data_ptr())
+            else:
+                assert b.dtype == np.float64 and b.flags.c_contiguous and b.size == count, (what, b.shape, count)
+                ptrs.append(b.ctypes.data)
+        return ptrs, bool(dev)
+
+    def _halo_order_in(self, bufs):
+        import torch
+        torch.cuda.current_stream(next(b for b in bufs if b is not None).device).synchronize()
+
+    def pack_halo_pair(self, axis, width=1, out=None):
+        """the edge strips of the live on-ocean planes for the east / north neighbour (hi) and the west / south one (lo).
+        out: (hi, lo), each a flat float64 numpy array, a torch tensor on the handle's device, or None for a side without a
+        neighbour; default two new numpy arrays.  Returns (hi, lo).  Device tensors: their pending work is waited for and
+        the strips are in them on return (nothing crosses the bus)."""
+        count = self.halo_buffer_count(axis, width)
+        if out is None:
+            out = (np.empty(count), np.empty(count))
+        ptrs, dev = self._halo_buffers(out, count, "pack_halo_pair")
+        if dev:
+            self._halo_order_in(out)
+        self._check(self.lib.kid_pack_halo_pair(self.h, int(axis), int(width), ptrs[0], ptrs[1], int(dev)), "kid_pack_halo_pair")
+        if dev:
+            self.sync()
+        return tuple(out)
+
+    def unpack_halo_pair(self, axis, from_lo, from_hi, width=1):
+        """the neighbours' strips into this handle's halo: from_lo (what the west / south neighbour packed as hi) and from_hi,
+        numpy arrays, torch device tensors or None for a missing side (that halo keeps its zeros)"""
+        count = self.halo_buffer_count(axis, width)
+        bufs = (from_lo, from_hi)
+        if from_lo is None and from_hi is None:
+            return
+        ptrs, dev = self._halo_buffers(bufs, count, "unpack_halo_pair")
+        if dev:
+            self._halo_order_in(bufs)
+        self._check(self.lib.kid_unpack_halo_pair(self.h, int(axis), int(width), ptrs[0], ptrs[1], int(dev)), "kid_unpack_halo_pair")
+        if dev:
+            self.sync()             # the tensors may be reused on return
+
     # ---- restart files (icebergs_fms2io.F90:124-631, 663-1049) ----
     def write_restart(self, directory):
         self._check(self.lib.kid_write_restart(self.h, str(directory).encode()), "kid_write_restart")

@@ -213,6 +213,41 @@ int kid_unpack_immigrants(kid_handle *h, const double *buf, int64_t n);
 int kid_pack_emigrants_pair(kid_handle *h, int32_t axis, double *buf_a, int64_t capacity_a, int64_t *n_a, double *buf_b, int64_t capacity_b, int64_t *n_b);
 int kid_unpack_immigrants_pair(kid_handle *h, const double *buf_a, int64_t n_a, const double *buf_b, int64_t n_b);
 
+/* ---- halo update of the on-ocean planes of a domain-decomposed model: mpp_update_domains(var_on_ocean, grd%domain) of
+ * sum_up_spread_fields (IB:6106-6107), split where the reference calls the message layer.  A berg writes the nine slots of its
+ * own cell only, so the 9-point sum (IB:6126-6131) of a cell on a tile's edge reads slots that belong to the neighbouring tile.
+ * The handle packs the edge strips of the live planes and unpacks the neighbours' strips into its halo; the caller moves the
+ * buffers, as with the berg migration above.  Per step of a tile, in the reference's order: kid_zero_accumulators,
+ * [kid_interp_gridded_fields_to_bergs], kid_evolve_icebergs, the berg exchange, [interp again], kid_thermodynamics,
+ * kid_calculate_mass_on_ocean, then per axis (0, then 1) kid_pack_halo_pair, send/recv, kid_unpack_halo_pair, then kid_step_gather.
+ *
+ * Buffer layout.  np = kid_halo_plane_count planes, in accumulator order from KID_A_MASS_ON_OCEAN; w = width,
+ * 1 <= w <= min(halo, nic, njc), anything else KID_EINVAL (and so is an axis other than 0 or 1).
+ *   axis 0 (east/west), rows jsc .. jec:          buf_hi (for the east neighbour) = columns iec-w+1 .. iec,
+ *                                                 buf_lo (for the west neighbour) = columns isc .. isc+w-1;
+ *       element order plane, j, i (i fastest), np * njc * w doubles each;
+ *       unpack writes from_lo into columns isc-w .. isc-1 and from_hi into iec+1 .. iec+w.
+ *   axis 1 (north/south), columns isc-w .. iec+w  (the corner columns axis 0 has just filled: a diagonal neighbour's corner arrives
+ *                                                 in two hops, as with mpp_update_domains):
+ *                                                 buf_hi = rows jec-w+1 .. jec, buf_lo = rows jsc .. jsc+w-1;
+ *       the same element order, np * w * (nic + 2w) doubles each;
+ *       unpack writes from_lo into rows jsc-w .. jsc-1 and from_hi into jec+1 .. jec+w.
+ * A NULL pointer: no neighbour on that side (NULL_PE).  Nothing is packed for it, and on unpack that halo keeps what it holds: the
+ * zero of the spreading's memset, which is what the halo of an undivided grid holds.
+ * One launch packs (unpacks) both directions of an axis for all live planes, on the handle's stream, behind the side stream.
+ * on_device: the buffers are device addresses (a torch tensor handed to RCCL, a GPU-aware MPI); the call only enqueues and the
+ * caller orders its own work behind the handle's stream.  Otherwise the strips go through a pinned staging buffer: the pack call
+ * returns when the data are in buf_hi / buf_lo, the unpack call when from_lo / from_hi may be reused.
+ * Not covered: find_melt_using_spread_mass on tiles (its two extra gathers inside kid_step_local would need the same update),
+ * the parity swap of a tripolar fold (IB:6110-6122), the forcing planes (the host owns them). */
+/* calculate_mass_on_ocean (IB:4984-...), the spreading half of kid_create_gridded_icebergs_fields: zero the 36 on-ocean planes,
+ * the spreading launch (with reproducible sums: its fold too), NO gather.  kid_step_gather is the other half. */
+int kid_calculate_mass_on_ocean(kid_handle *h);
+int kid_halo_plane_count(kid_handle *h, int32_t *nplanes);   /* 9 (mass_on_ocean only) or 36: the rule of kid_accum_live_count */
+int kid_halo_buffer_count(kid_handle *h, int32_t axis, int32_t width, int64_t *count);   /* doubles per direction */
+int kid_pack_halo_pair(kid_handle *h, int32_t axis, int32_t width, double *buf_hi, double *buf_lo, int32_t on_device);
+int kid_unpack_halo_pair(kid_handle *h, int32_t axis, int32_t width, const double *from_lo, const double *from_hi, int32_t on_device);
+
 /* kid_set_forcing_device + kid_zero_accumulators for the step about to start, as one per-cell launch (fields == NULL
  * keeps the current forcing and only zeroes); the following kid_step_local does not zero again. */
 int kid_step_prepare(kid_handle *h, const double *const device_fields[KID_NFORCING]);
