@@ -198,8 +198,9 @@ __global__ void __launch_bounds__(256) calve_emit_kernel(const DevGrid g, const 
     Env e{};
     {
       int err = 0; bool bail = false;
-      if (!pos_within_cell<false>(g, p, cell, blon, blat, i, j, xi, yj, err, bail)) nerr += 1.;  // FATAL IB:6281
-      if (!p.old_interp_flds_order) interp_flds(p, cell, xi, yj, e);                             // IB:6353-6364
+      // (once per calving cell: the reference's own operations, so that what a new berg starts with equals the reference's bit for bit)
+      if (!pos_within_cell<false, 0, false, true>(g, p, cell, blon, blat, i, j, xi, yj, err, bail)) nerr += 1.;  // FATAL IB:6281
+      if (!p.old_interp_flds_order) interp_flds<0, false, true>(p, cell, xi, yj, e);                             // IB:6353-6364
     }
     double st[KID_NCLASSES];
 #pragma unroll

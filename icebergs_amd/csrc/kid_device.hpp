@@ -147,6 +147,12 @@ __device__ __forceinline__ double kid_sqrt(double x) {
 }
 #endif
 
+// IEEE = true: the operation as the reference performs it (a rounded product and a rounded sum, the correctly rounded quotient and
+// root) in this build as well -- for the cold callers whose results are held to the reference bit for bit (the calving source's
+// in-cell position and stored environment); IEEE = false: the forms above.
+template <bool IEEE> __device__ __forceinline__ double kid_fma_t(double a, double b, double c) { if constexpr (IEEE) return a * b + c; else return kid_fma(a, b, c); }
+template <bool IEEE> __device__ __forceinline__ double kid_div_t(double a, double b) { if constexpr (IEEE) return a / b; else return kid_div(a, b); }
+
 // The same for a sum of squares of speeds (never negative, never infinite): the seed is taken of max(x, 1e-300), so x = 0 comes
 // out as 0 through the arithmetic itself (g = 0 * 1e150 = 0 in every step) and the three selects of the general form go; the
 // result is the same bits as kid_sqrt(x) for every x that is 0 or >= 1e-300.
@@ -430,6 +436,7 @@ __device__ __forceinline__ bool is_point_in_cell(const DevGrid &g, const Corners
 }
 
 // FW:6439-6534.  Returns false on the reference's FATAL paths.
+template <bool IEEE = false>
 __device__ __forceinline__ bool calc_xiyj(double x1, double x2, double x3, double x4, double y1, double y2, double y3, double y4,
                                           double x, double y, double &xi, double &yj, double Lx) {
   const double alpha = x2 - x1, delta = y2 - y1, beta = x4 - x1, epsilon = y4 - y1;
@@ -442,18 +449,18 @@ __device__ __forceinline__ bool calc_xiyj(double x1, double x2, double x3, doubl
   if (fabs(a) > 1.e-12) {
     const double d = 0.25 * (b * b) - a * c;
     if (d >= 0.) {
-      const double sd = kid_sqrt(d);
-      const Rcp ra = kid_rcp(a);
-      const double yy1 = -(0.5 * b + sd) * ra, yy2 = -(0.5 * b - sd) * ra;
+      double yy1, yy2;
+      if constexpr (IEEE) { const double sd = sqrt(d); yy1 = -(0.5 * b + sd) / a; yy2 = -(0.5 * b - sd) / a; }
+      else { const double sd = kid_sqrt(d); const Rcp ra = kid_rcp(a); yy1 = -(0.5 * b + sd) * ra; yy2 = -(0.5 * b - sd) * ra; }
       yj = (fabs(yy1 - 0.5) < fabs(yy2 - 0.5)) ? yy1 : yy2;
     } else { ok = false; yj = -999.; }
   } else {
-    yj = (b != 0.) ? kid_div(-c, b) : 0.;
+    yj = (b != 0.) ? kid_div_t<IEEE>(-c, b) : 0.;
   }
   a = (alpha + gamma * yj);
   b = (delta + kappa * yj);
-  if (a != 0.) xi = kid_div(dx - beta * yj, a);
-  else if (b != 0.) xi = kid_div(dy - epsilon * yj, b);
+  if (a != 0.) xi = kid_div_t<IEEE>(dx - beta * yj, a);
+  else if (b != 0.) xi = kid_div_t<IEEE>(dy - epsilon * yj, b);
   else {
     c = (epsilon * alpha - beta * delta) + (epsilon * gamma - beta * kappa) * yj;
     if (c != 0.) xi = (epsilon * dx - beta * dy) / c; else { ok = false; xi = -999.; }
@@ -498,7 +505,7 @@ __device__ __forceinline__ RectInv rect_inv(const Corners &q) {
   r.ra = kid_rcp(r.alpha); r.rb = kid_rcp(r.b);
   return r;
 }
-template <bool FAST, int K = 0, bool HAVE_RI = false, class CELL>
+template <bool FAST, int K = 0, bool HAVE_RI = false, bool IEEE = false, class CELL>
 __device__ __forceinline__ bool pos_within_cell(const DevGrid &g, const kid_params &p, const CELL &cell, double x, double y, int i, int j,
                                                 double &xi, double &yj, int &err, bool &bail, const RectInv ri = RectInv{}) {
   if constexpr (FAST) {
@@ -534,10 +541,10 @@ __device__ __forceinline__ bool pos_within_cell(const DevGrid &g, const kid_para
     const double ddx = fabs(q.lon11 - q.lon01), ddy = fabs(q.lat11 - q.lat10);
     const double x1 = q.lon11 - (ddx / 2), y1 = q.lat11 - (ddy / 2);
     const double Delta_x = mod_around(x, x1, g.Lx) - x1;
-    xi = kid_div(Delta_x, ddx) + 0.5;
-    yj = kid_div(y - y1, ddy) + 0.5;
+    xi = kid_div_t<IEEE>(Delta_x, ddx) + 0.5;
+    yj = kid_div_t<IEEE>(y - y1, ddy) + 0.5;
   } else if (!g.latlon || dmax(dmax(dmax(q.lat00, q.lat10), q.lat11), q.lat01) < 89.999) {
-    if (!calc_xiyj(q.lon00, q.lon10, q.lon11, q.lon01, q.lat00, q.lat10, q.lat11, q.lat01, x, y, xi, yj, g.Lx)) err = 1;
+    if (!calc_xiyj<IEEE>(q.lon00, q.lon10, q.lon11, q.lon01, q.lat00, q.lat10, q.lat11, q.lat01, x, y, xi, yj, g.Lx)) err = 1;
   } else {  // polar cell: co-latitude tangent plane (FW:6359-6404), cold and out of line
     if (FAST) { bail = true; return false; }
     else pos_within_polar_cell(g, p, q, x, y, xi, yj, err);
@@ -564,12 +571,14 @@ __device__ __forceinline__ void bilin_lonlat(const DevGrid &g, const kid_params 
 // need_ice = false (wave-uniform): no berg of the wave sits in a cell with sea ice (hi = 0: c_ice = 0, IB:2129), so the ice
 // velocity multiplies 0 wherever it goes and is not interpolated -- bitwise the same accelerations
 // NANFREE: the caller has checked that the cell's stencil values hold no NaN (hot evolve: PkCell::hotok)
-template <int K = 0, bool NANFREE = false, class CELL>
+// IEEE: the reference's own operations (no fused multiply-add, every cell rotated), kid_fma_t above
+template <int K = 0, bool NANFREE = false, bool IEEE = false, class CELL>
 __device__ __forceinline__ void interp_flds(const kid_params &p, const CELL &cell, double xi, double yj, Env &e, bool need_ice = true) {
   double wx1, wx0, wy1, wy0;  // weights of columns i / i-1 and rows j / j-1 (FW:7081-7087)
   if (Sw<K>::old_bug_bilin(p)) { wx1 = 1. - xi; wx0 = xi; wy1 = 1. - yj; wy0 = yj; }
   else { wx1 = xi; wx0 = 1. - xi; wy1 = yj; wy0 = 1. - yj; }
-#define KID_BIL(f) kid_fma(kid_fma(cell.vel(3, f), wx1, cell.vel(2, f) * wx0), wy1, kid_fma(cell.vel(1, f), wx1, cell.vel(0, f) * wx0) * wy0)
+#define KID_F(a_, b_, c_) kid_fma_t<IEEE>(a_, b_, c_)
+#define KID_BIL(f) KID_F(KID_F(cell.vel(3, f), wx1, cell.vel(2, f) * wx0), wy1, KID_F(cell.vel(1, f), wx1, cell.vel(0, f) * wx0) * wy0)
   // A cell whose four corners carry cos = 1, sin = 0 (every cell of an unrotated grid; elsewhere all but the displaced-pole
   // patches) is not rotated at all: the reference interpolates cos to 1 or 1 - 2^-53 (the weights' own rounding) and multiplies
   // by it; here such a cell's velocities pass through, in both builds alike (a per-cell property: the result does not depend on
@@ -577,7 +586,7 @@ __device__ __forceinline__ void interp_flds(const kid_params &p, const CELL &cel
 #ifdef KID_EXACT_MATH
   const bool unrot = false;
 #else
-  const bool unrot = cell.unrot();
+  const bool unrot = IEEE ? false : cell.unrot();
 #endif
   const bool all_unrot = __ballot(!unrot) == 0ull;   // wave-uniform: nothing to rotate in this wave
   double cos_rot = 1., sin_rot = 0.;
@@ -601,25 +610,25 @@ __device__ __forceinline__ void interp_flds(const kid_params &p, const CELL &cel
     const bool up = yj >= 0.5;
     const int k = up ? 0 : 1;
     const double wa = yj + (up ? -0.5 : 0.5), wb = (up ? 1.5 : 0.5) - yj;
-    const double hxp = kid_fma(wa, cell.ddx(k), wb * cell.ddx(k + 1));
-    const double hxm = kid_fma(wa, cell.ddx(k + 3), wb * cell.ddx(k + 4));
-    ssh_x = kid_fma(xi, hxp, (1. - xi) * hxm);
+    const double hxp = KID_F(wa, cell.ddx(k), wb * cell.ddx(k + 1));
+    const double hxm = KID_F(wa, cell.ddx(k + 3), wb * cell.ddx(k + 4));
+    ssh_x = KID_F(xi, hxp, (1. - xi) * hxm);
   }
   {
     const bool up = xi >= 0.5;
     const int k = up ? 0 : 1;
     const double wa = xi + (up ? -0.5 : 0.5), wb = (up ? 1.5 : 0.5) - xi;
-    const double hyp = kid_fma(wa, cell.ddy(k), wb * cell.ddy(k + 1));
-    const double hym = kid_fma(wa, cell.ddy(k + 3), wb * cell.ddy(k + 4));
-    ssh_y = kid_fma(yj, hyp, (1. - yj) * hym);
+    const double hyp = KID_F(wa, cell.ddy(k), wb * cell.ddy(k + 1));
+    const double hym = KID_F(wa, cell.ddy(k + 3), wb * cell.ddy(k + 4));
+    ssh_y = KID_F(yj, hyp, (1. - yj) * hym);
   }
   // rotate to lat-lon (IB:4953-4967)
   if (!all_unrot) {
     double t, r0, r1;
-    t = uo; r0 = kid_fma(cos_rot, t, sin_rot * vo); r1 = kid_fma(cos_rot, vo, -(sin_rot * t)); if (!unrot) { uo = r0; vo = r1; }
-    if (need_ice) { t = ui; r0 = kid_fma(cos_rot, t, sin_rot * vi); r1 = kid_fma(cos_rot, vi, -(sin_rot * t)); if (!unrot) { ui = r0; vi = r1; } }
-    t = ua; r0 = kid_fma(cos_rot, t, sin_rot * va); r1 = kid_fma(cos_rot, va, -(sin_rot * t)); if (!unrot) { ua = r0; va = r1; }
-    t = ssh_x; r0 = kid_fma(cos_rot, t, sin_rot * ssh_y); r1 = kid_fma(cos_rot, ssh_y, -(sin_rot * t)); if (!unrot) { ssh_x = r0; ssh_y = r1; }
+    t = uo; r0 = KID_F(cos_rot, t, sin_rot * vo); r1 = KID_F(cos_rot, vo, -(sin_rot * t)); if (!unrot) { uo = r0; vo = r1; }
+    if (need_ice) { t = ui; r0 = KID_F(cos_rot, t, sin_rot * vi); r1 = KID_F(cos_rot, vi, -(sin_rot * t)); if (!unrot) { ui = r0; vi = r1; } }
+    t = ua; r0 = KID_F(cos_rot, t, sin_rot * va); r1 = KID_F(cos_rot, va, -(sin_rot * t)); if (!unrot) { ua = r0; va = r1; }
+    t = ssh_x; r0 = KID_F(cos_rot, t, sin_rot * ssh_y); r1 = KID_F(cos_rot, ssh_y, -(sin_rot * t)); if (!unrot) { ssh_x = r0; ssh_y = r1; }
   }
   if constexpr (!NANFREE) {   // IB:4869-4870
     if (ssh_x != ssh_x) ssh_x = 0.;
@@ -627,6 +636,7 @@ __device__ __forceinline__ void interp_flds(const kid_params &p, const CELL &cel
   }
   e.uo = uo; e.vo = vo; e.ui = ui; e.vi = vi; e.ua = ua; e.va = va; e.ssh_x = ssh_x; e.ssh_y = ssh_y;
   e.sst = cell.t0(0); e.sss = cell.t0(1); e.cn = cell.t0(2); e.hi = cell.t0(3); e.od = cell.t0(4);
+#undef KID_F
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -163,6 +163,9 @@ static int mts_check_timeout(kid_handle *h) {   // (after a stream synchronisati
 static int mts_build_order(kid_handle *h) {
   const long long n = h->n;
   if (n == 0) { h->mts.nperm = 0; return KID_OK; }
+  // the key kernels below read the device copy of the berg table: on a handle's first step nothing has written it yet when
+  // kid_set_conglom_ids or the prologue come here before their mts_refresh (single-time-step scheme with contact)
+  { const int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
   int cur = 0;
   // The five `inorder` keys (start_lat, start_lon, start_mass, start_day, start_year) never change while bonds exist
   // (rows do not move, nothing re-stamps a bonded berg), only the cell does: the order by those five is built once per
