@@ -192,6 +192,7 @@ static int budget_sweep(kid_handle *h, double res[BUD_NRES]) {
 
 extern "C" int kid_budget(kid_handle *h, kid_budget_out *out) {
   if (!h || !out) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_budget"); if (rc_h) return rc_h; }
   double res[BUD_NRES];
   const int rc = budget_sweep(h, res);
   if (rc) return rc;
@@ -213,6 +214,7 @@ extern "C" int kid_budget(kid_handle *h, kid_budget_out *out) {
 extern "C" int kid_stock(kid_handle *h, int32_t index, double *value) {
   if (!h || !value) return KID_EINVAL;
   *value = 0.0;   // `case default`, IB:8128-8129
+  { const int rc_h = halo_rows_refuse(h, "kid_stock"); if (rc_h) return rc_h; }
   if (index != KID_STOCK_WATER && index != KID_STOCK_HEAT) { h->err = "kid_stock: index is neither KID_STOCK_WATER nor KID_STOCK_HEAT"; return KID_EINVAL; }
   double res[BUD_NRES];
   const int rc = budget_sweep(h, res);
@@ -226,6 +228,7 @@ extern "C" int kid_stock(kid_handle *h, int32_t index, double *value) {
 
 extern "C" int kid_incr_mass(kid_handle *h, double *mass, int32_t on_device, int32_t ni, int32_t nj) {
   if (!h || !mass) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_incr_mass"); if (rc_h) return rc_h; }
   const kid_grid_desc &d = h->gd;
   const int nic = d.iec - d.isc + 1, njc = d.jec - d.jsc + 1;
   if (ni != nic || nj != njc) { h->err = "kid_incr_mass: the plane must cover the computational domain (isc:iec, jsc:jec)"; return KID_EINVAL; }

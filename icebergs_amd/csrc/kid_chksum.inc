@@ -18,6 +18,7 @@ static inline uint64_t chk_bits(double x) { uint64_t u; std::memcpy(&u, &x, size
 
 extern "C" int kid_bergs_chksum(kid_handle *h, int64_t out[6]) {
   if (!h || !out) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_bergs_chksum"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = join_side(h); if (rc_j) return rc_j; }
   { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }

@@ -73,6 +73,7 @@ extern "C" {
 
 int kid_calculate_mass_on_ocean(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_calculate_mass_on_ocean"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));  // IB:4984-4987
   return launch_berg<PH_SPREAD>(h);

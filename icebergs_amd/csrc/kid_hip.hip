@@ -417,6 +417,8 @@ struct kid_handle {
   bool mig_mode = false;                   // the host exchanges bergs with other handles (kid_migrate.inc): dead rows waiting to be packed are kept
   int32_t *d_keep = nullptr;               // layout flags of such a run (keep_flags_kernel)
   long long mig_last[2] = {0, 0};          // records of the last pack call per slot: sizes the pinned staging buffer
+  long long halo_last[2] = {0, 0};         // the same for kid_pack_halo_bergs_pair
+  bool halo_rows_live = false;             // copies of the neighbours' bergs are resident (kid_halo_bergs.inc): set by an unpack call, cleared by the evolve that retires them
   bool env_ever_stored = false;            // some launch since the last upload wrote berg%uo..od
   bool env_off_requested = false;          // kid_set_store_environment(h, 0)
   double *d_orient = nullptr;              // bond-derived hexagon orientation per berg (mts / interacting bergs)
@@ -502,6 +504,14 @@ struct kid_handle {
       return KID_EHIP;                                                                        \
     }                                                                                         \
   } while (0)
+
+// Halo rows (kid_halo_bergs.inc) are force sources for one kid_evolve_icebergs and nothing else: between the unpack that
+// brought them and the evolve that retires them, whatever would melt, spread, count, move or write them out is refused.
+static int halo_rows_refuse(kid_handle *h, const char *what) {
+  if (!h->halo_rows_live) return KID_OK;
+  h->err = std::string(what) + ": halo rows are resident (copies of the neighbours' bergs, kid_unpack_immigrants); the next kid_evolve_icebergs retires them";
+  return KID_EINVAL;
+}
 
 static DevGrid dev_grid(const kid_handle *h) {
   DevGrid g;
@@ -1007,7 +1017,7 @@ int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
   h->tail_valid = false; h->env_ever_stored = false;
   if (h->bp.orient) { h->bp.orient = nullptr; h->tables_dirty = true; }
   h->n = host->n;
-  h->visited = false; h->have_bonds = false;
+  h->visited = false; h->have_bonds = false; h->halo_rows_live = false;
   KID_HIP(h, hipStreamSynchronize(h->stream));
   return KID_OK;
 }
@@ -1178,6 +1188,7 @@ static bool rebin_fusable(const kid_handle *h) {
 }
 int kid_move_berg_between_cells(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_move_berg_between_cells"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
   { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (re-binning twice in a row: the second one sorts the rows of the first)
@@ -1568,6 +1579,7 @@ int kid_evolve_icebergs_mts(kid_handle *h);
 int kid_evolve_icebergs_interactive(kid_handle *h);
 int kid_interp_gridded_fields_to_bergs(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_interp_gridded_fields_to_bergs"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   int rc = launch_berg<PH_INTERP>(h);
   if (rc || !h->params.mts) return rc;
@@ -1584,6 +1596,7 @@ int kid_evolve_icebergs(kid_handle *h) {
 }
 int kid_thermodynamics(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_thermodynamics"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   // IB:2872-2873
   KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_UVEL_ON_OCEAN * h->ncell, 0, 18 * h->ncell * sizeof(double), h->stream));
@@ -1643,6 +1656,7 @@ static int fl_assign_ids(kid_handle *h, long long n_old, int m) {
 }
 int kid_footloose_calving(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_footloose_calving"); if (rc_h) return rc_h; }
   if (!h->params.footloose || h->n == 0) return KID_OK;
   KID_HIP(h, hipSetDevice(h->device));
   int rc = repro_refuse(h);
@@ -1711,6 +1725,7 @@ static int launch_gather(kid_handle *h) {
 }
 int kid_create_gridded_icebergs_fields(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_create_gridded_icebergs_fields"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));  // IB:4984-4987
   int rc = launch_berg<PH_SPREAD>(h);
@@ -1728,6 +1743,7 @@ extern "C" {
 
 int kid_step_local(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_step_local"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   int rc = h->acc_prezeroed ? KID_OK : kid_zero_accumulators(h);  // kid_step_prepare has done it for this step
   h->acc_prezeroed = false;
@@ -1845,6 +1861,7 @@ int kid_step_local(kid_handle *h) {
 }
 int kid_step_gather(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_step_gather"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
   int rc = launch_gather(h);
   if (rc) return rc;
@@ -1952,5 +1969,6 @@ int kid_profile_get(kid_handle *h, double *berg_ms, int64_t *launches, double *a
 #include "kid_restart.inc"
 #include "kid_traj.inc"
 #include "kid_migrate.inc"
+#include "kid_halo_bergs.inc"
 #include "kid_halo.inc"
 #include "kid_chksum.inc"

@@ -25,6 +25,23 @@ __device__ __forceinline__ int mig_selected(const MigSel &s, const BergPtrs &b, 
   if (which >= 0 && s.has_halo && b.f[KID_B_HALO_BERG][k] >= 0.5) which = -1;              // FW:3027
   return which;
 }
+// pack_berg_into_buffer2 without bonds, FW:3268-3301: one record.  `halo` goes where halo_berg goes: the row's own for an
+// emigrant, 1 for the copy update_halo_icebergs sends (FW:1903-1906)
+__device__ __forceinline__ void mig_write_record(double *o, const BergPtrs &b, long long k, double halo) {
+  const int64_t id = b.id[k];
+  int c = 0;
+  o[c++] = b.f[KID_B_LON][k]; o[c++] = b.f[KID_B_LAT][k]; o[c++] = b.f[KID_B_UVEL][k]; o[c++] = b.f[KID_B_VVEL][k];
+  o[c++] = b.f[KID_B_UVEL_PREV][k]; o[c++] = b.f[KID_B_VVEL_PREV][k]; o[c++] = b.f[KID_B_XI][k]; o[c++] = b.f[KID_B_YJ][k];
+  o[c++] = b.f[KID_B_START_LON][k]; o[c++] = b.f[KID_B_START_LAT][k]; o[c++] = (double)b.i[KID_BI_START_YEAR][k]; o[c++] = b.f[KID_B_START_DAY][k];
+  o[c++] = b.f[KID_B_START_MASS][k]; o[c++] = b.f[KID_B_MASS][k]; o[c++] = b.f[KID_B_THICKNESS][k]; o[c++] = b.f[KID_B_WIDTH][k];
+  o[c++] = b.f[KID_B_LENGTH][k]; o[c++] = b.f[KID_B_FL_K][k]; o[c++] = b.f[KID_B_MASS_SCALING][k]; o[c++] = b.f[KID_B_MASS_OF_BITS][k];
+  o[c++] = b.f[KID_B_MASS_OF_FL_BITS][k]; o[c++] = b.f[KID_B_MASS_OF_FL_BERGY_BITS][k]; o[c++] = b.f[KID_B_HEAT_DENSITY][k];
+  o[c++] = (double)b.i[KID_BI_INE][k]; o[c++] = (double)b.i[KID_BI_JNE][k];
+  o[c++] = b.f[KID_B_AXN][k]; o[c++] = b.f[KID_B_AYN][k]; o[c++] = b.f[KID_B_BXN][k]; o[c++] = b.f[KID_B_BYN][k];
+  o[c++] = halo; o[c++] = b.f[KID_B_STATIC_BERG][k];
+  o[c++] = (double)(int32_t)(id >> 32); o[c++] = (double)(int32_t)(id & 0xffffffffll);                                   // split_id, FW:3297-3299
+  o[c++] = b.f[KID_B_OD][k];
+}
 }  // namespace
 
 // pack_berg_into_buffer2 without bonds, FW:3268-3301, into a host-visible staging buffer: the first `cap` selected rows are
@@ -44,20 +61,7 @@ __global__ void __launch_bounds__(256) pack_emigrants_kernel(const BergPtrs b, c
     if (which == q) slot = (long long)base + __popcll(m & ((1ull << lane) - 1ull));
   }
   if (which < 0 || slot >= out.cap[which]) return;
-  double *o = out.buf[which] + (size_t)slot * MIG_WIDTH;
-  const int64_t id = b.id[k];
-  int c = 0;
-  o[c++] = b.f[KID_B_LON][k]; o[c++] = b.f[KID_B_LAT][k]; o[c++] = b.f[KID_B_UVEL][k]; o[c++] = b.f[KID_B_VVEL][k];
-  o[c++] = b.f[KID_B_UVEL_PREV][k]; o[c++] = b.f[KID_B_VVEL_PREV][k]; o[c++] = b.f[KID_B_XI][k]; o[c++] = b.f[KID_B_YJ][k];
-  o[c++] = b.f[KID_B_START_LON][k]; o[c++] = b.f[KID_B_START_LAT][k]; o[c++] = (double)b.i[KID_BI_START_YEAR][k]; o[c++] = b.f[KID_B_START_DAY][k];
-  o[c++] = b.f[KID_B_START_MASS][k]; o[c++] = b.f[KID_B_MASS][k]; o[c++] = b.f[KID_B_THICKNESS][k]; o[c++] = b.f[KID_B_WIDTH][k];
-  o[c++] = b.f[KID_B_LENGTH][k]; o[c++] = b.f[KID_B_FL_K][k]; o[c++] = b.f[KID_B_MASS_SCALING][k]; o[c++] = b.f[KID_B_MASS_OF_BITS][k];
-  o[c++] = b.f[KID_B_MASS_OF_FL_BITS][k]; o[c++] = b.f[KID_B_MASS_OF_FL_BERGY_BITS][k]; o[c++] = b.f[KID_B_HEAT_DENSITY][k];
-  o[c++] = (double)b.i[KID_BI_INE][k]; o[c++] = (double)b.i[KID_BI_JNE][k];
-  o[c++] = b.f[KID_B_AXN][k]; o[c++] = b.f[KID_B_AYN][k]; o[c++] = b.f[KID_B_BXN][k]; o[c++] = b.f[KID_B_BYN][k];
-  o[c++] = b.f[KID_B_HALO_BERG][k]; o[c++] = b.f[KID_B_STATIC_BERG][k];
-  o[c++] = (double)(int32_t)(id >> 32); o[c++] = (double)(int32_t)(id & 0xffffffffll);                                   // split_id, FW:3297-3299
-  o[c++] = b.f[KID_B_OD][k];
+  mig_write_record(out.buf[which] + (size_t)slot * MIG_WIDTH, b, k, b.f[KID_B_HALO_BERG][k]);
 }
 // delete_iceberg_from_list for the rows just packed (FW:3034): gone, and never selected again
 __global__ void __launch_bounds__(256) consume_emigrants_kernel(const BergPtrs b, const MigSel s, long long n) {
@@ -102,8 +106,9 @@ __global__ void __launch_bounds__(64) unpack_immigrants_kernel(const DevGrid g, 
     for (int jj = g.jsd + 1; jj <= g.jed && !found; ++jj)
       for (int ii = g.isd + 1; ii <= g.ied && !found; ++ii)
         if (holds(ii, jj)) { i = ii; j = jj; found = true; }
-  // the kernels trust cell indices up to one cell outside the computational domain (as kid_upload_bergs checks)
-  if (found && (i < g.isc - 1 || i > g.iec + 1 || j < g.jsc - 1 || j > g.jec + 1)) found = false;
+  // the kernels trust cell indices up to one cell outside the computational domain (as kid_upload_bergs checks); a halo row
+  // (r[29] = 1, kid_halo_bergs.inc) sits anywhere in the data domain: only the cell tables of the interacting scheme see it
+  if (found && !(r[29] >= 0.5) && (i < g.isc - 1 || i > g.iec + 1 || j < g.jsc - 1 || j > g.jec + 1)) found = false;
   if (!found) { atomicAdd(nerr, 1); b.i[KID_BI_ALIVE][k] = 0; b.i[KID_BI_INE][k] = g.isc; b.i[KID_BI_JNE][k] = g.jsc; return; }
   double xi = 0., yj = 0.;
   int err = 0; bool bail = false;
@@ -113,6 +118,7 @@ __global__ void __launch_bounds__(64) unpack_immigrants_kernel(const DevGrid g, 
 
 extern "C" {
 
+static int halo_bergs_supported(kid_handle *h, const char *what);   // kid_halo_bergs.inc
 static int mig_supported(kid_handle *h) {
   h->mig_mode = true;   // from the first migration call on, dead rows waiting to be packed survive tail drops, compaction and re-binning (layout_flags)
   if (h->have_bonds || h->params.iceberg_bonds_on || h->params.mts || h->params.dem) {
@@ -146,6 +152,7 @@ static int pack_core(kid_handle *h, int nd, const int32_t *dir, double *const *b
     if (!n[q] || dir[q] < KID_DIR_E || dir[q] > KID_DIR_S || capacity[q] < 0 || (capacity[q] > 0 && !buf[q])) return KID_EINVAL;
     *n[q] = 0;
   }
+  { const int rc_h = halo_rows_refuse(h, "kid_pack_emigrants"); if (rc_h) return rc_h; }
   { const int rc = mig_supported(h); if (rc) return rc; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = lanes_drain(h); if (rc) return rc; }   // a berg the slow lane still owes a step has not left yet
@@ -207,6 +214,10 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   { const int rc = mig_supported(h); if (rc) return rc; }
   const int64_t m = m_a + m_b;
   if (m == 0) return KID_OK;
+  bool any_halo = false;   // copies of a neighbour's bergs (update_halo_icebergs FW:1800-2131): only the scheme kid_halo_bergs.inc covers takes them
+  for (int64_t q = 0; q < m_a && !any_halo; ++q) any_halo = buf_a[(size_t)q * MIG_WIDTH + 29] >= 0.5;
+  for (int64_t q = 0; q < m_b && !any_halo; ++q) any_halo = buf_b[(size_t)q * MIG_WIDTH + 29] >= 0.5;
+  if (any_halo) { const int rc = halo_bergs_supported(h, "kid_unpack_immigrants"); if (rc) return rc; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = lanes_drain(h); if (rc) return rc; }
   { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
@@ -244,6 +255,7 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   KID_HIP(h, hipStreamSynchronize(h->stream));
   const int nerr = (int)(*mig_pinned_word(h) & 0xffffffffull);
   h->n += m;
+  if (any_halo) h->halo_rows_live = true;
   h->tail_valid = false; h->static_rows_n = -1; h->rp.srows_n = -1;
   if (!h->params.old_interp_flds_order) h->env_ever_stored = true;
   if (nerr > 0) { h->err = "kid_unpack_immigrants: can not find a cell to place berg in! (" + std::to_string(nerr) + " bergs dropped)"; return KID_EINVAL; }

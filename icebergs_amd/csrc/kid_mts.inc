@@ -1625,6 +1625,7 @@ __global__ void __launch_bounds__(256) sts_ia_velocity_kernel(const DevGrid g, c
   if (k >= n) return;
   const BergPtrs &b = *bt; const kid_params &p = *pp; const MtsDev &m = *mt;
   if (MI(KID_BI_ALIVE, k) == 0 || !(MF(KID_B_STATIC_BERG, k) < 0.5)) return;
+  if (MF(KID_B_HALO_BERG, k) >= 0.5) return;   // a neighbour tile's berg (kid_halo_bergs.inc): a force source, its owner steps it
   const double dt = p.dt, dt_2 = 0.5 * dt;
   const double lonn = MF(KID_B_LON, k), latn = MF(KID_B_LAT, k);
   double axn = MF(KID_B_AXN, k), ayn = MF(KID_B_AYN, k), bxn = MF(KID_B_BXN, k), byn = MF(KID_B_BYN, k);
@@ -1654,7 +1655,11 @@ __global__ void __launch_bounds__(256) sts_ia_position_kernel(const DevGrid g, c
   const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
   if (k >= n) return;
   const BergPtrs &b = *bt; const kid_params &p = *pp; const MtsDev &m = *mt;
-  if (MI(KID_BI_ALIVE, k) == 0 || !(MF(KID_B_STATIC_BERG, k) < 0.5)) return;
+  if (MI(KID_BI_ALIVE, k) == 0) return;
+  // a halo row has served (the velocity sweep is done): retired, never moved, and its cell put back inside as the emigrant
+  // packer does with a packed row, so that nothing takes it for a leaver waiting to be packed
+  if (MF(KID_B_HALO_BERG, k) >= 0.5) { MI(KID_BI_ALIVE, k) = 0; MI(KID_BI_INE, k) = g.isc; MI(KID_BI_JNE, k) = g.jsc; return; }
+  if (!(MF(KID_B_STATIC_BERG, k) < 0.5)) return;
   const double uvel1 = MF(KID_B_UVEL, k), vvel1 = MF(KID_B_VVEL, k);
   const LonLat q = verlet_position(g, p, MF(KID_B_LON, k), MF(KID_B_LAT, k), uvel1, vvel1, MF(KID_B_AXN, k), MF(KID_B_AYN, k), MF(KID_B_BXN, k), MF(KID_B_BYN, k), p.dt);
   double lonn = q.lon, latn = q.lat;

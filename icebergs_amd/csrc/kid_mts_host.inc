@@ -520,6 +520,7 @@ int kid_evolve_icebergs_interactive(kid_handle *h) {
   hipLaunchKernelGGL(sts_ia_velocity_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
   hipLaunchKernelGGL(sts_ia_position_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
   KID_HIP(h, hipGetLastError());
+  h->halo_rows_live = false;   // the position sweep has retired them
   return mts_fold_scalars(h);
 }
 // the `Visited` block for interacting bergs without MTS (IB:5415-5418)

@@ -459,6 +459,7 @@ static void restart_calving_file(const kid_handle *h, const std::vector<double> 
 // <dir>/calving.res.nc (buckets, stored heat, the id counters, the running means)
 int kid_write_restart(kid_handle *h, const char *dir) {
   if (!h || !dir) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_write_restart"); if (rc_h) return rc_h; }
   int64_t n_slots = 0, n_alive = 0;
   int rc = kid_num_bergs(h, &n_slots, &n_alive);
   if (rc) return rc;

@@ -185,6 +185,7 @@ static int btraj_reserve(kid_handle *h, long long want) {   // room for `want` b
 
 int kid_record_posn(kid_handle *h) {
   if (!h) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_record_posn"); if (rc_h) return rc_h; }
   if (!h->traj_on) { h->err = "kid_set_traj_params must be called first"; return KID_EINVAL; }
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc = join_side(h); if (rc) return rc; }
@@ -233,6 +234,7 @@ int kid_num_traj_records(kid_handle *h, int64_t *n) {
 
 int kid_write_trajectories(kid_handle *h, const char *path) {
   if (!h || !path) return KID_EINVAL;
+  { const int rc_h = halo_rows_refuse(h, "kid_write_trajectories"); if (rc_h) return rc_h; }
   if (!h->traj_on) { h->err = "kid_set_traj_params must be called first"; return KID_EINVAL; }
   int64_t nrec = 0;
   int rc = kid_num_traj_records(h, &nrec);

@@ -18,6 +18,11 @@ exchanges in their places; for it the tile also offers the phases (`zero_accumul
 `calculate_mass_on_ocean`, `gather`), its `params`, and `halo_buffer_count(axis, width)`, `pack_halo_pair(axis, width, sides)`
 -> (strip for the east/north neighbour, strip for the west/south one; None where `sides` says there is no neighbour) and
 `unpack_halo_pair(axis, from_lo, from_hi, width)`.
+
+The third exchange is for interacting bergs: `TileExchange.update_halo_bergs` brings copies of the neighbours' bergs next to the
+shared edges (update_halo_icebergs, FW:1800-2131) so that contact forces cross tile edges, and `TileExchange.step_interactive`
+is the step that uses it.  The tile offers `pack_halo_bergs_pair(axis, width, sides)` -> (records for the east/north neighbour,
+for the west/south one) and `set_conglom_ids()`; the records come in through `unpack_pair`.
 """
 import numpy as np
 import torch
@@ -76,6 +81,12 @@ class HipTile:
 
     def pack_pair(self, axis):
         return self.ib.pack_emigrants_pair(axis)
+
+    def pack_halo_bergs_pair(self, axis, width=0, sides=(True, True)):
+        return self.ib.pack_halo_bergs_pair(axis, width, sides)
+
+    def set_conglom_ids(self):
+        self.ib.set_conglom_ids()
 
     def unpack_pair(self, from_lo, from_hi):
         self.ib.unpack_immigrants_pair(from_lo, from_hi)
@@ -174,6 +185,48 @@ class TileExchange:
             from_lo, from_hi = self._swap(to_hi, hi, to_lo, lo)
             if len(from_lo) or len(from_hi):
                 tile.unpack_pair(from_lo, from_hi)            # from the west / south first, FW:3064, 3160
+
+    def update_halo_bergs(self, tile, width=None):
+        """update_halo_icebergs (FW:1800-2131) for this rank's tile: copies of the neighbours' bergs next to the shared edges
+        arrive as halo rows, force sources for the evolve that follows and retires them.  East/west, then north/south over the
+        columns of the whole data domain, which carry what the first pass has brought: a diagonal neighbour's bergs arrive in
+        two hops.  Counts, then records, as the migration.  width None: the grid's halo."""
+        if self.cyclic_x:
+            raise ValueError("TileExchange.update_halo_bergs does not cover cyclic_x (update_latlon, IB:5467; DESIGN 7.6, out of scope)")
+        w = 0 if width is None else int(width)
+        for axis, (dx, dy) in enumerate(((1, 0), (0, 1))):
+            hi, lo = self.neighbour(dx, dy), self.neighbour(-dx, -dy)
+            if hi is None and lo is None:
+                continue
+            to_hi, to_lo = tile.pack_halo_bergs_pair(axis, w, (hi is not None, lo is not None))
+            from_lo, from_hi = self._swap(to_hi, hi, to_lo, lo)
+            if len(from_lo) or len(from_hi):
+                tile.unpack_pair(from_lo, from_hi)
+
+    def step_interactive(self, tile, width=1, halo_width=None):
+        """one step of icebergs_run for a tile of unbonded interacting bergs under the single-time-step Verlet scheme.
+        The halo bergs are taken right before the evolve (the reference takes them before the thermodynamics of the step
+        before, IB:5462, so that a copy carries its owner's size of one melt earlier): a tile run sees what the undivided run sees."""
+        p = tile.params
+        if not p.interactive_icebergs_on:
+            raise ValueError("TileExchange.step_interactive needs interactive_icebergs_on; TileExchange.step covers the rest")
+        for switch in ("find_melt_using_spread_mass", "mts", "iceberg_bonds_on", "footloose", "Runge_not_Verlet"):
+            if getattr(p, switch):
+                raise ValueError("TileExchange.step_interactive does not cover %s on tiles (DESIGN 7.6, out of scope)" % switch)
+        tile.zero_accumulators()                 # IB:5125-5156
+        if not p.old_interp_flds_order:
+            tile.interp()                        # IB:5423
+        self.update_halo_bergs(tile, halo_width)  # IB:5462, moved here
+        if p.contact_distance > 0.0 or p.contact_spring_coef != p.spring_coef:
+            tile.set_conglom_ids()               # IB:5470-5471, with the halo rows resident
+        tile.evolve()                            # IB:5433; retires the halo rows
+        self.exchange(tile)                      # IB:5447
+        if not p.old_interp_flds_order:
+            tile.interp()                        # IB:5473
+        tile.thermodynamics()                    # IB:5505
+        tile.calculate_mass_on_ocean()           # IB:5512 -> IB:4984
+        self.update_halos(tile, width)           # IB:6106-6107
+        tile.gather()                            # IB:6126-6150, 3419-3488
 
     def _swap_halo(self, to_hi, hi, to_lo, lo, count):
         """the strips of one axis (numpy, `count` doubles each): `to_hi` to rank `hi`, `to_lo` to rank `lo`; returns

@@ -24,6 +24,7 @@ module kid_hip_mod
   public :: kid_calving, kid_get_calving
   public :: kid_write_restart, kid_read_restart, kid_bergs_chksum
   public :: kid_buffer_width, kid_pack_emigrants, kid_unpack_immigrants, kid_pack_emigrants_pair, kid_unpack_immigrants_pair
+  public :: kid_pack_halo_bergs_pair, kid_halo_berg_count
   public :: kid_traj_params, kid_set_traj_params, kid_record_posn, kid_write_trajectories, kid_write_bond_trajectories
   public :: kid_zero_accumulators, kid_interp_gridded_fields_to_bergs, kid_evolve_icebergs, kid_footloose_calving
   public :: kid_set_footloose_step, kid_get_footloose_step
@@ -176,6 +177,21 @@ module kid_hip_mod
       type(c_ptr), value :: h
       real(c_double), intent(in) :: buf_a(*), buf_b(*)
       integer(c_int64_t), value :: n_a, n_b
+    end function
+    integer(c_int) function kid_pack_halo_bergs_pair(h, axis, width, buf_hi, capacity_hi, n_hi, buf_lo, capacity_lo, n_lo) &
+        bind(C, name='kid_pack_halo_bergs_pair')
+      import :: c_int, c_ptr, c_int32_t, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: axis              ! 0: east (hi) + west (lo), 1: north (hi) + south (lo)
+      integer(c_int32_t), value :: width             ! 0: the grid's halo (update_halo_icebergs FW:1818)
+      type(c_ptr), value :: buf_hi, buf_lo           ! c_loc(obuffer%data), c_null_ptr where there is no neighbour (NULL_PE)
+      integer(c_int64_t), value :: capacity_hi, capacity_lo
+      integer(c_int64_t), intent(out) :: n_hi, n_lo
+    end function
+    integer(c_int) function kid_halo_berg_count(h, n) bind(C, name='kid_halo_berg_count')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), intent(out) :: n
     end function
     integer(c_int) function kid_unpack_immigrants(h, buf, n) bind(C, name='kid_unpack_immigrants')
       import :: c_int, c_ptr, c_int64_t, c_double

@@ -208,6 +208,29 @@ class Icebergs:
             self._check(self.lib.kid_unpack_immigrants_pair(self.h, _dp(a) if a.size else None, a.shape[0] if a.size else 0,
                                                             _dp(b) if b.size else None, b.shape[0] if b.size else 0), "kid_unpack_immigrants_pair")
 
+    def pack_halo_bergs_pair(self, axis, width=0, sides=(True, True)):
+        """copies of the bergs next to the two edges of `axis` for the neighbours' halos (update_halo_icebergs FW:1800-2131), as
+        records with halo_berg = 1: (for the east / north neighbour, for the west / south one); the rows stay as they are.
+        width 0: the grid's halo; sides: False where there is no neighbour (nothing is selected for it)"""
+        n = [C.c_int64(), C.c_int64()]
+        if getattr(self, "_halo_berg_buf", None) is None:
+            self._halo_berg_buf = [np.empty((4096, 34)) for _ in range(2)]
+        for attempt in range(2):
+            a, b = self._halo_berg_buf
+            rc = self.lib.kid_pack_halo_bergs_pair(self.h, int(axis), int(width), _dp(a) if sides[0] else None, a.shape[0], C.byref(n[0]),
+                                                   _dp(b) if sides[1] else None, b.shape[0], C.byref(n[1]))
+            if rc != -4 or attempt:
+                break
+            self._halo_berg_buf = [np.empty((max(2 * q.value, x.shape[0]), 34)) for q, x in zip(n, (a, b))]   # KID_ECAPACITY: nothing was packed
+        self._check(rc, "kid_pack_halo_bergs_pair")
+        return self._halo_berg_buf[0][:n[0].value].copy(), self._halo_berg_buf[1][:n[1].value].copy()
+
+    def halo_berg_count(self):
+        """resident halo rows: more than 0 only between an unpack of halo records and the next kid_evolve_icebergs"""
+        n = C.c_int64()
+        self._check(self.lib.kid_halo_berg_count(self.h, C.byref(n)), "kid_halo_berg_count")
+        return n.value
+
     def unpack_immigrants(self, buf):
         buf = np.ascontiguousarray(buf, dtype=np.float64)
         if buf.size:

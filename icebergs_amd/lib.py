@@ -28,6 +28,7 @@ SYMBOLS = [
     "kid_set_traj_params", "kid_record_posn", "kid_num_traj_records", "kid_write_trajectories",
     "kid_num_bond_traj_records", "kid_write_bond_trajectories",
     "kid_buffer_width", "kid_pack_emigrants", "kid_unpack_immigrants", "kid_pack_emigrants_pair", "kid_unpack_immigrants_pair",
+    "kid_pack_halo_bergs_pair", "kid_halo_berg_count",
     "kid_calculate_mass_on_ocean", "kid_halo_plane_count", "kid_halo_buffer_count", "kid_pack_halo_pair", "kid_unpack_halo_pair",
 ]
 
@@ -103,6 +104,8 @@ def load():
     lib.kid_unpack_immigrants.argtypes = [H, C.POINTER(C.c_double), C.c_int64]
     lib.kid_pack_emigrants_pair.argtypes = [H, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]
     lib.kid_unpack_immigrants_pair.argtypes = [H, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_int64]
+    lib.kid_pack_halo_bergs_pair.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64)]
+    lib.kid_halo_berg_count.argtypes = [H, C.POINTER(C.c_int64)]
     lib.kid_calculate_mass_on_ocean.argtypes = [H]
     lib.kid_halo_plane_count.argtypes = [H, C.POINTER(C.c_int32)]
     lib.kid_halo_buffer_count.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]

@@ -212,6 +212,29 @@ int kid_unpack_immigrants(kid_handle *h, const double *buf, int64_t n);
  * unpack loops, FW:3064-3097).  Same results as the single calls. */
 int kid_pack_emigrants_pair(kid_handle *h, int32_t axis, double *buf_a, int64_t capacity_a, int64_t *n_a, double *buf_b, int64_t capacity_b, int64_t *n_b);
 int kid_unpack_immigrants_pair(kid_handle *h, const double *buf_a, int64_t n_a, const double *buf_b, int64_t n_b);
+/* Halo bergs (update_halo_icebergs FW:1800-2131): interactive_force (IB:480-607) walks the lists of the neighbouring cells, which on
+ * a tile's edge belong to another rank; the reference fills them with copies of the neighbour's bergs.  kid_pack_halo_bergs_pair
+ * packs the copies both ways along an axis in one launch, in the record of the migration calls with halo_berg (real 30) = 1; the
+ * source rows stay as they are.  w = width (0: the grid's halo), 2 <= w <= min(halo, nic, njc), else KID_EINVAL.
+ *   axis 0, live rows in cells jsc..jec:  buf_hi (for the east neighbour) = columns iec-w+2 .. iec (w-1 of them),
+ *                                         buf_lo (for the west neighbour) = columns isc .. isc+w-1      (FW:1896, 1911);
+ *   axis 1, live rows in columns isd..ied (the halo rows axis 0 has just brought included: a diagonal neighbour's bergs arrive
+ *           in two hops):                 buf_hi (north) = rows jec-w+2 .. jec, buf_lo (south) = rows jsc .. jsc+w-1 (FW:1981, 1995).
+ * A NULL buffer: no neighbour on that side, nothing is selected for it.  *n = rows selected; if *n > capacity nothing is packed
+ * and KID_ECAPACITY is returned.  The neighbour hands the records to kid_unpack_immigrants(_pair), which finds their cells
+ * anywhere in its data domain.  Call order per step: axis 0 pack, send/recv, unpack, axis 1 pack, send/recv, unpack, then
+ * kid_evolve_icebergs.
+ * A halo row is a force source for that one kid_evolve_icebergs: its velocity sweep skips the row, its position sweep retires it
+ * (dead, its cell put back inside; the next compaction or re-binning drops it).  From the unpack to that evolve
+ * kid_interp_gridded_fields_to_bergs, kid_thermodynamics, the spreading and gather calls, kid_step_local, kid_run_step,
+ * kid_budget, kid_stock, kid_incr_mass, kid_pack_emigrants*, kid_move_berg_between_cells, kid_footloose_calving, kid_calving,
+ * kid_write_restart, kid_bergs_chksum, kid_record_posn and kid_write_trajectories return KID_EINVAL.  The reference takes the copies before thermodynamics (IB:5462)
+ * and uses them in the next step's evolve; these calls do not fix the moment.
+ * Covered: interactive_icebergs_on under the single-time-step Verlet scheme without bonds.  iceberg_bonds_on, mts, dem,
+ * footloose, find_melt_using_spread_mass, static_icebergs, periodic_reentry, a namelist without interactive_icebergs_on and Runge_not_Verlet:
+ * KID_EUNSUPPORTED from the pack call, and from an unpack call that meets a record with halo_berg = 1. */
+int kid_pack_halo_bergs_pair(kid_handle *h, int32_t axis, int32_t width, double *buf_hi, int64_t capacity_hi, int64_t *n_hi, double *buf_lo, int64_t capacity_lo, int64_t *n_lo);
+int kid_halo_berg_count(kid_handle *h, int64_t *n);   /* resident halo rows (alive, halo_berg = 1) */
 
 /* ---- halo update of the on-ocean planes of a domain-decomposed model: mpp_update_domains(var_on_ocean, grd%domain) of
  * sum_up_spread_fields (IB:6106-6107), split where the reference calls the message layer.  A berg writes the nine slots of its
