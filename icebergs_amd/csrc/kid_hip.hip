@@ -1598,6 +1598,12 @@ int kid_thermodynamics(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_thermodynamics"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
+  // find_melt_using_spread_mass: the gridded mass before the melt (grd%spread_mass_old, IB:5490-5503) is gathered inside
+  // kid_step_local only; without it the gather would hand back the bergs' own melt as if the switch were off
+  if (h->params.find_melt_using_spread_mass && (!h->d_spread_mass_old || h->d_spread_mass_old == h->d_spread_mass_old_own)) {
+    h->err = "find_melt_using_spread_mass: the phase entry points do not gather spread_mass_old (IB:5490-5503); use kid_run_step / kid_step_local";
+    return KID_EUNSUPPORTED;
+  }
   // IB:2872-2873
   KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_UVEL_ON_OCEAN * h->ncell, 0, 18 * h->ncell * sizeof(double), h->stream));
   return launch_berg<PH_THERMO>(h);
@@ -1804,7 +1810,8 @@ int kid_step_local(kid_handle *h) {
     return p.old_interp_flds_order ? launch_berg<PH_THERMO | PH_SPREAD>(h, n_old, appended) : launch_berg<PH_INTERP | PH_THERMO | PH_SPREAD>(h, n_old, appended);
   }
   if (p.footloose) {  // phase by phase (KID_FL_UNFUSED, static bergs): three launches
-    rc = launch_berg<PH_INTERP | PH_EVOLVE>(h);
+    // static_icebergs: evolve_icebergs is not called (IB:5428-5436); the calving that follows still is (IB:5453)
+    rc = p.static_icebergs ? launch_berg<PH_INTERP>(h) : launch_berg<PH_INTERP | PH_EVOLVE>(h);
     if (rc) return rc;
     rc = kid_footloose_calving(h);
     if (rc) return rc;

@@ -391,7 +391,8 @@ int kid_bind_accum_buffer(kid_handle *h, void *dev_ptr, int64_t count);
  * Iceberg_melt_without_decay, spread_mass_tmp (IB:3411-3413) live in two planes that kid_step_local fills and kid_step_gather
  * reads.  Both are 9-point gathers of per-cell sums, i.e. linear in what each GPU's bergs contribute: a sharded run binds a
  * buffer of its own here (2 planes of ni*nj fp64) and all-reduces it between kid_step_local and kid_step_gather together with
- * the accumulator planes.  NULL returns to the handle's own planes. */
+ * the accumulator planes.  NULL returns to the handle's own planes.  The phase entry points do not fill them: with the switch on
+ * and no buffer bound here, kid_thermodynamics returns KID_EUNSUPPORTED instead of a melt flux computed as if it were off. */
 int kid_bind_spread_mass_old(kid_handle *h, void *dev_ptr, int64_t count);
 
 /* ---- measurement: HIP-event timing of the per-berg kernel on the launch stream ---- */
