@@ -192,7 +192,7 @@ static int bond_half_width(double thr, double ext, int ncells) {
   return w < (double)ncells ? (int)w : ncells;
 }
 static int bond_words(kid_handle *h) {
-  if (!h->d_bond_words) KID_HIP(h, hipMalloc(&h->d_bond_words, BI_WORDS * sizeof(unsigned long long)));
+  if (!h->d_bond_words) KID_HIP(h, h->mem.dev(h->d_bond_words, BI_WORDS));
   KID_HIP(h, hipMemsetAsync(h->d_bond_words, 0, BI_WORDS * sizeof(unsigned long long), h->stream));
   return KID_OK;
 }

@@ -148,7 +148,7 @@ static int budget_ensure(kid_handle *h) {
   if (h->d_budget) return KID_OK;
   const size_t nb_b = ((size_t)h->capacity + 255) / 256;
   const size_t nb_c = ((size_t)(h->gd.iec - h->gd.isc + 1) * (size_t)(h->gd.jec - h->gd.jsc + 1) + 255) / 256;
-  KID_HIP(h, hipMalloc(&h->d_budget, ((size_t)BUD_NQ_BERG * nb_b + (size_t)BUD_NQ_CELL * nb_c + BUD_NRES) * sizeof(double)));
+  KID_HIP(h, h->mem.dev(h->d_budget, (size_t)BUD_NQ_BERG * nb_b + (size_t)BUD_NQ_CELL * nb_c + BUD_NRES));
   return KID_OK;
 }
 
@@ -171,8 +171,8 @@ static int budget_sweep(kid_handle *h, double res[BUD_NRES]) {
     { const int rc = repro_static_order(h); if (rc) return rc; }
     hipLaunchKernelGGL(budget_live_key_kernel, dim3((unsigned)nblk_b), block, 0, h->stream, (const int32_t *)h->bp.i[KID_BI_ALIVE], (const int32_t *)h->bp.i[KID_BI_INE],
                        (const int32_t *)h->bp.i[KID_BI_JNE], (const int *)h->rp.srows, d.isc, d.iec, d.jsc, d.jec, h->rp.k32[0], h->rp.rows[0], n);
-    size_t bytes = h->rp.tmp_bytes;
-    KID_HIP(h, rocprim::radix_sort_pairs(h->rp.tmp, bytes, h->rp.k32[0], h->rp.k32[1], h->rp.rows[0], h->rp.rows[1], (size_t)n, 0, 1, h->stream));
+    size_t bytes = h->rp.tmp.bytes;
+    KID_HIP(h, rocprim::radix_sort_pairs(h->rp.tmp.p, bytes, h->rp.k32[0], h->rp.k32[1], h->rp.rows[0], h->rp.rows[1], (size_t)n, 0, 1, h->stream));
     order = h->rp.rows[1];
   }
   if (nblk_b > 0) {
@@ -238,7 +238,7 @@ extern "C" int kid_incr_mass(kid_handle *h, double *mass, int32_t on_device, int
   const size_t bytes = (size_t)nic * (size_t)njc * sizeof(double);
   double *plane = mass;
   if (!on_device) {
-    if (!h->d_budget_plane) KID_HIP(h, hipMalloc(&h->d_budget_plane, bytes));
+    if (!h->d_budget_plane) KID_HIP(h, h->mem.dev(h->d_budget_plane, bytes / sizeof(double)));
     plane = h->d_budget_plane;
     KID_HIP(h, hipMemcpyAsync(plane, mass, bytes, hipMemcpyHostToDevice, h->stream));
   }

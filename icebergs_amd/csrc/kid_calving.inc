@@ -273,15 +273,14 @@ __global__ void __launch_bounds__(256) calve_emit_kernel(const DevGrid g, const 
 static int calving_ensure(kid_handle *h) {
   if (h->d_calv_state) return KID_OK;
   const size_t planes = 2 + 2 * KID_NCLASSES + 1 + 2;  // calving, hflx, stored_ice, real_calving, stored_heat, two running means
-  KID_HIP(h, hipMalloc(&h->d_calv_state, planes * h->ncell * sizeof(double)));
-  KID_HIP(h, hipMemset(h->d_calv_state, 0, planes * h->ncell * sizeof(double)));
+  KID_HIP(h, h->mem.dev(h->d_calv_state, planes * h->ncell, 0));
   // one small block: the KID_NCALV_SCALARS sums, then the row cursor and the calving-cell count (one memset, one copy back)
-  KID_HIP(h, hipMalloc(&h->d_calv_scal, (KID_NCALV_SCALARS + 1) * sizeof(double)));
-  KID_HIP(h, hipHostMalloc((void **)&h->calv_host, (KID_NCALV_SCALARS + 1) * sizeof(double)));
-  KID_HIP(h, hipMalloc(&h->d_calv_flag, h->ncell)); KID_HIP(h, hipMemset(h->d_calv_flag, 0, h->ncell));
-  KID_HIP(h, hipMalloc(&h->d_calv_list, h->ncell * sizeof(int2)));
-  { const size_t nb = (h->ncell + 255) / 256; KID_HIP(h, hipMalloc(&h->d_calv_part, nb * (CALV_PART_ACC + CALV_PART_CALVE) * sizeof(double))); }
-  KID_HIP(h, hipDeviceSynchronize());
+  KID_HIP(h, h->mem.dev(h->d_calv_scal, KID_NCALV_SCALARS + 1));
+  KID_HIP(h, h->mem.pinned(h->calv_host, KID_NCALV_SCALARS + 1));
+  KID_HIP(h, h->mem.dev(h->d_calv_flag, h->ncell, 0));
+  KID_HIP(h, h->mem.dev(h->d_calv_list, h->ncell));
+  KID_HIP(h, h->mem.dev(h->d_calv_part, (h->ncell + 255) / 256 * (CALV_PART_ACC + CALV_PART_CALVE)));
+  KID_HIP(h, hipStreamSynchronize(h->stream));
   return KID_OK;
 }
 static double *calv_plane(kid_handle *h, int which) { return h->d_calv_state + (size_t)which * h->ncell; }
@@ -350,11 +349,7 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   CalvingDev a{};
   if (in->on_device) { a.calving_in = in->calving; a.hflx_in = in->calving_hflx; }
   else {
-    if (2 * n0 > h->ingest_stage_count) {
-      if (h->d_ingest_stage) { KID_HIP(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_ingest_stage); h->d_ingest_stage = nullptr; }
-      KID_HIP(h, hipMalloc(&h->d_ingest_stage, 2 * n0 * sizeof(double)));
-      h->ingest_stage_count = 2 * n0;
-    }
+    { const int rc = ingest_stage_reserve(h, 2 * n0); if (rc) return rc; }
     KID_HIP(h, hipMemcpyAsync(h->d_ingest_stage, in->calving, n0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     KID_HIP(h, hipMemcpyAsync(h->d_ingest_stage + n0, in->calving_hflx, n0 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     a.calving_in = h->d_ingest_stage; a.hflx_in = h->d_ingest_stage + n0;

@@ -54,9 +54,9 @@ static int halo_refuse(kid_handle *h, const char *who) {
 static int halo_stage(kid_handle *h, long long count) {   // pinned staging the device addresses directly (grows)
   if (count <= h->halo_capacity) return KID_OK;
   KID_HIP(h, hipStreamSynchronize(h->stream));
-  if (h->halo_buf) (void)hipHostFree(h->halo_buf);
-  h->halo_buf = nullptr; h->halo_capacity = 0;
-  KID_HIP(h, hipHostMalloc((void **)&h->halo_buf, (size_t)count * sizeof(double)));
+  h->halo_capacity = 0;
+  KID_HIP(h, h->mem.drop(h->halo_buf));
+  KID_HIP(h, h->mem.pinned(h->halo_buf, (size_t)count));
   h->halo_capacity = count;
   return KID_OK;
 }

@@ -382,128 +382,7 @@ __global__ void __launch_bounds__(256) fill_i32_kernel(int32_t *p, int32_t v, lo
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-struct kid_handle {
-  int device = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  kid_grid_desc gd{};
-  kid_params params{};
-  int ni = 0, nj = 0;
-  size_t ncell = 0;
-  int64_t capacity = 0, n = 0;
-  // device memory
-  double *d_static[KID_NGRID_STATIC] = {}, *d_forcing[KID_NFORCING] = {};
-  VelRec *d_vel = nullptr; TrcRec *d_trc = nullptr; GeoRec *d_geo = nullptr; double *d_hotok = nullptr; double *d_latref = nullptr;
-  // the accumulator block: KID_NSCALAR step scalars, then KID_NACC planes of ncell (scalars first, so that they and the planes a
-  // step really fills -- a prefix -- are ONE contiguous range for the all-reduce); d_acc points at plane 0
-  double *d_acc_own = nullptr, *d_acc = nullptr;
-  double *d_out = nullptr;                        // KID_NOUT*ncell
-  double *d_totals = nullptr;                     // KID_NSCALAR running totals (the block's scalars are per-step)
-  BergPtrs bp{};
-  BergPtrs *d_bp = nullptr;      // device copy of the field-pointer table
-  kid_params *d_params = nullptr; // device copy of the parameter block
-  DevGrid *d_grid = nullptr;      // device copy of the grid descriptor (berg_kernel reads it as a table)
-  bool tables_dirty = true;
-  double *d_spare_f64 = nullptr; unsigned *d_pos = nullptr, *d_flag = nullptr; void *d_scan_tmp = nullptr; size_t scan_tmp_bytes = 0;
-  unsigned long long *d_count = nullptr;
-  int *d_redo_list = nullptr, *d_redo_count = nullptr;  // bergs the FAST build hands to the general build
-  // pipelined launches (kid_set_side_stream): the population goes through the hot build in two halves on the main
-  // stream while the general build of each half runs on the side stream, under the hot build of the other half
-  hipStream_t side_stream = nullptr; bool pipelined = false;
-  int *d_redo_list2 = nullptr, *d_redo_count2 = nullptr;
-  int *d_redo_cnt[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [part][parity]: a step's counters are zeroed by its prepass
-  int redo_parity = 0; bool redo_prezeroed = false, acc_prezeroed = false;
-  bool uploaded_nonzero[KID_NB_F64] = {};  // fields that held anything but zeros at the last upload
-  bool tail_valid = false;                 // the dead rows are exactly the tail (true between a re-binning and the next launch)
-  bool mig_mode = false;                   // the host exchanges bergs with other handles (kid_migrate.inc): dead rows waiting to be packed are kept
-  int32_t *d_keep = nullptr;               // layout flags of such a run (keep_flags_kernel)
-  long long mig_last[2] = {0, 0};          // records of the last pack call per slot: sizes the pinned staging buffer
-  long long halo_last[2] = {0, 0};         // the same for kid_pack_halo_bergs_pair
-  bool halo_rows_live = false;             // copies of the neighbours' bergs are resident (kid_halo_bergs.inc): set by an unpack call, cleared by the evolve that retires them
-  bool env_ever_stored = false;            // some launch since the last upload wrote berg%uo..od
-  bool env_off_requested = false;          // kid_set_store_environment(h, 0)
-  double *d_orient = nullptr;              // bond-derived hexagon orientation per berg (mts / interacting bergs)
-  hipEvent_t evF[2] = {nullptr, nullptr}, evG[2] = {nullptr, nullptr}; bool evG_live[2] = {false, false};
-  // "slow lane" schedule (kid_set_side_stream mode 2, launch_berg_lanes)
-  int side_mode = 0; int *d_lane = nullptr, *d_lane_alt = nullptr; hipEvent_t evR = nullptr; int lane_step = 1; bool lanes_active = false, carry_valid = false, evC_live = false;
-  hipEvent_t evC = nullptr, evP = nullptr;
-  VelRec *d_vel2 = nullptr; TrcRec *d_trc2 = nullptr; DevGrid *d_grid2 = nullptr; int forc_parity = 0;  // forcing records of the odd steps
-  double *d_pkt[2] = {nullptr, nullptr};   // gathered cell packets of the hot build, one set per parity of the forcing records
-  // A/B switches for measurements and tests, read from the environment ONCE, when the handle is created (nothing on the
-  // stepping path calls getenv): KID_MTS_NO_GRAPH, KID_STABLE_RESORT, KID_NO_PLAIN_BUILD, KID_FL_UNFUSED, KID_NEW_ORDER_UNFUSED,
-  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
-  // fall-back), KID_MTS_POLL_LIMIT (spins before a lane of that kernel gives up: tests of the time-out)
-  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false, rebin_eager = false;
-                     int mts_fused_blocks_cap = 0, mts_poll_limit = 0; } dbg;
-  int32_t *d_iceberg_counter = nullptr;  // grd%iceberg_counter_grd (FW:1017)
-  bool fl_place_warm = false;
-  unsigned fl_step = 0;                  // footloose passes so far: third counter word of the child-placement generator (kid_rng.h)
-  int *d_fl_cursor = nullptr;
-  int32_t *d_fl_head = nullptr, *d_fl_next = nullptr; int64_t *d_fl_newid = nullptr; long long fl_ev_capacity = 0;   // fl_assign_ids_*
-  unsigned *d_key[2] = {nullptr, nullptr}, *d_idx[2] = {nullptr, nullptr};  // radix-sort ping-pong buffers
-  void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
-  double *d_perm_spare = nullptr;
-  BergPtrs bp_alt{};            // second set of field arrays: the re-binning writes all fields there in one launch, then swaps
-  // A re-binning whose permutation is known (rebin_plan) but whose copy has not run (rebin_apply): the next whole-population
-  // plain hot build takes its rows through the permutation itself (launch_berg); anything else that looks at rows, row
-  // numbers or the pointer tables runs the copy first (rebin_flush).  Nothing of this state is visible from outside.
-  bool rebin_pending = false;
-  int64_t rebin_fused_count = 0;   // re-binnings taken by that launch so far (kid_rebin_fused_count: tests, A/B runs)
-  struct RebinPlan { PermTable t{}; int moved_f[KID_NB_F64] = {}; int nmf = 0; unsigned long long moved = 0ull; const unsigned *perm = nullptr; long long n = 0; } rplan;
-  RebinTab *d_rb = nullptr;     // device table of the re-binning instance of the plain hot builds
-  unsigned *d_cell_hist = nullptr; void *d_cscan_tmp = nullptr; size_t cscan_tmp_bytes = 0; bool stable_resort = false;
-  int resort_interval = 16, steps_since_sort = 0;
-  // multiple time stepping / DEM
-  MtsDev mts{}; MtsDev *d_mts = nullptr;
-  int mb = 0; bool mts_ready = false, mts_dirty = true, have_bonds = false, visited = false;
-  unsigned long long *d_key64[2] = {nullptr, nullptr}; int *d_rows[2] = {nullptr, nullptr};
-  int *d_static_rows = nullptr; long long static_rows_n = -1, static_rows_cap = 0;   // rows ordered by the five static `inorder` keys (mts_build_order)
-  unsigned long long *d_last_key = nullptr; int *d_order_flag = nullptr; long long order_n = -1;   // cell key of every row at the last sort: an unchanged population keeps its order
-  unsigned long long *d_bond_sig = nullptr; bool labels_stale = true;   // per-berg signature of what the conglomerate labelling reads (set_conglom_ids skips itself while nothing changes)
-  MtsDev mts_shadow{}; bool mts_shadow_valid = false;   // what d_mts holds (the table is re-uploaded only when it differs)
-  int conglom_batch = 8;                                // label-propagation sweeps launched before the first convergence check (set_conglom_ids)
-  void *d_mts_tmp = nullptr; size_t mts_tmp_bytes = 0;
-  unsigned long long *d_bond_words = nullptr;           // counters of kid_initialize_bonds / kid_count_bonds (kid_bond_init.inc)
-  double bond_ext[2] = {0., 0.}; bool bond_ext_valid = false;   // smallest cell extents in metres of the static grid (bond_extents)
-  hipGraphExec_t sub_graph_exec = nullptr;  // the captured sub-step loop of evolve_icebergs_mts
-  long long sub_graph_n = -1; int sub_graph_steps = 0; bool sub_graph_pair = false; double sub_graph_dt = 0.; hipStream_t sub_graph_stream = nullptr;
-  bool use_graph = true;
-  int fused_blocks[2] = {0, 0};             // co-resident workgroups of mts_substeps_kernel<4> / <8> (0: not asked yet)
-  bool fused_ran = false;                   // a fused sub-step launch since the last look at its time-out counter
-  Flags flags{0, 0, 1, 0, 0};
-  // trajectories (kid_traj.inc): one buffer per sampled field, grown on demand
-  bool traj_on = false; kid_traj_params traj_params{}; double *d_traj_f[64] = {}; double *d_traj_day = nullptr; int64_t *d_traj_id = nullptr;
-  int32_t *d_traj_year = nullptr, *d_traj_nbonds = nullptr; unsigned long long *d_traj_cursor = nullptr; long long traj_capacity = 0, traj_count_bound = 0; int traj_nf = 0;
-  double *d_mig_buf = nullptr; long long mig_capacity = 0; unsigned long long *mig_word = nullptr;   // pinned staging of kid_pack_emigrants / kid_unpack_immigrants
-  double *halo_buf = nullptr; long long halo_capacity = 0;   // pinned staging of kid_pack_halo_pair / kid_unpack_halo_pair (kid_halo.inc)
-  double *d_btraj_f[16] = {}; int64_t *d_btraj_id[2] = {}; int32_t *d_btraj_i[2] = {}; long long btraj_capacity = 0, btraj_count_bound = 0;   // bond samples
-  double *d_spread_mass_old = nullptr;   // grd%spread_mass_old (find_melt_using_spread_mass, IB:5495-5497) + spread_mass_tmp; the handle's own or the caller's (kid_bind_spread_mass_old)
-  double *d_spread_mass_old_own = nullptr;
-  bool have_static = false, have_forcing = false, have_planes = false;  // have_planes: d_forcing holds all eleven planes
-  double *d_calv_state = nullptr, *d_calv_scal = nullptr, *d_calv_part = nullptr; unsigned char *d_calv_flag = nullptr; int2 *d_calv_list = nullptr; double *calv_host = nullptr; kid_calving_params calv_params{};  // kid_calving (kid_calving.inc)
-  bool calving_on = false, calving_first_call = true, rmean_init = false, rmean_hflx_init = false;
-  double *d_ingest_stage = nullptr; size_t ingest_stage_count = 0; unsigned long long *d_ingest_key = nullptr;  // kid_ingest_forcing
-  bool profile = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  double berg_ms = 0., all_ms = 0.; int64_t berg_launches = 0;
-  // reproducible sums (kid_set_reproducible_sums, kid_repro.inc): staging table, row keys / masks, the static canonical order
-  // (valid while srows_n == n; reset wherever rows move), sort buffers, cell starts, per-cell heat and its block sums
-  bool repro = false;
-  struct Repro { double *stage = nullptr; int32_t *key = nullptr; unsigned long long *mask = nullptr; int *srows = nullptr; long long srows_n = -1;
-                 unsigned long long *k64[2] = {nullptr, nullptr}; int *rows[2] = {nullptr, nullptr}; unsigned *k32[2] = {nullptr, nullptr};
-                 int *cs = nullptr; double *cell_heat = nullptr, *part = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0; } rp;
-  double *d_budget = nullptr, *d_budget_plane = nullptr;   // kid_budget.inc: block partials + results of the sweep; staging plane of kid_incr_mass
-  std::string err;
-};
-
-#define KID_HIP(h, call)                                                                      \
-  do {                                                                                        \
-    hipError_t e__ = (call);                                                                  \
-    if (e__ != hipSuccess) {                                                                  \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                          \
-      return KID_EHIP;                                                                        \
-    }                                                                                         \
-  } while (0)
+#include "kid_handle.hpp"
 
 // Halo rows (kid_halo_bergs.inc) are force sources for one kid_evolve_icebergs and nothing else: between the unpack that
 // brought them and the evolve that retires them, whatever would melt, spread, count, move or write them out is refused.
@@ -614,7 +493,9 @@ int kid_exp_timing(unsigned long long *out, int reset) {
   return KID_OK;
 }
 #endif
-const char *kid_last_error(const kid_handle *h) { return h ? h->err.c_str() : "null handle"; }
+// kid_destroy reports a failed free through kid_last_error(NULL), to the thread that called it: the handle is gone by then
+static thread_local std::string destroy_err;
+const char *kid_last_error(const kid_handle *h) { return h ? h->err.c_str() : destroy_err.empty() ? "null handle" : destroy_err.c_str(); }
 
 int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capacity, int device, kid_handle **out) {
   if (!grid || !params || !out || capacity <= 0) return KID_EINVAL;
@@ -646,145 +527,61 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   if (const char *e = getenv("KID_MTS_POLL_LIMIT")) h->dbg.mts_poll_limit = atoi(e);
   KID_HIP(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
   h->stream = h->own_stream;
-  for (int k = 0; k < KID_NGRID_STATIC; ++k) { KID_HIP(h, hipMalloc(&h->d_static[k], h->ncell * sizeof(double))); KID_HIP(h, hipMemset(h->d_static[k], 0, h->ncell * sizeof(double))); }
-  for (int k = 0; k < KID_NFORCING; ++k) { KID_HIP(h, hipMalloc(&h->d_forcing[k], h->ncell * sizeof(double))); KID_HIP(h, hipMemset(h->d_forcing[k], 0, h->ncell * sizeof(double))); }
-  KID_HIP(h, hipMalloc(&h->d_vel, h->ncell * sizeof(VelRec)));
-  KID_HIP(h, hipMalloc(&h->d_trc, h->ncell * sizeof(TrcRec)));
-  KID_HIP(h, hipMalloc(&h->d_geo, h->ncell * sizeof(GeoRec)));
-  KID_HIP(h, hipMalloc(&h->d_hotok, h->ncell * sizeof(double)));
-  KID_HIP(h, hipMemset(h->d_hotok, 0, h->ncell * sizeof(double)));
-  if (grid->grid_is_latlon) KID_HIP(h, hipMalloc(&h->d_latref, 2 * h->ncell * sizeof(double)));   // DevGrid::latref
-  const size_t accn = (size_t)KID_NACC * h->ncell + KID_NSCALAR;
-  KID_HIP(h, hipMalloc(&h->d_acc_own, accn * sizeof(double)));
-  KID_HIP(h, hipMemset(h->d_acc_own, 0, accn * sizeof(double)));
+  const size_t cap = (size_t)capacity;
+  for (auto &plane : h->d_static) KID_HIP(h, h->mem.dev(plane, h->ncell, 0));
+  for (auto &plane : h->d_forcing) KID_HIP(h, h->mem.dev(plane, h->ncell, 0));
+  for (VelRec **q : {&h->d_vel, &h->d_vel2}) KID_HIP(h, h->mem.dev(*q, h->ncell));   // (the second set: forcing records of the odd steps)
+  for (TrcRec **q : {&h->d_trc, &h->d_trc2}) KID_HIP(h, h->mem.dev(*q, h->ncell));
+  KID_HIP(h, h->mem.dev(h->d_geo, h->ncell));
+  KID_HIP(h, h->mem.dev(h->d_hotok, h->ncell, 0));
+  if (grid->grid_is_latlon) KID_HIP(h, h->mem.dev(h->d_latref, 2 * h->ncell));   // DevGrid::latref
+  KID_HIP(h, h->mem.dev(h->d_acc_own, (size_t)KID_NACC * h->ncell + KID_NSCALAR, 0));
   h->d_acc = h->d_acc_own + KID_NSCALAR;
-  KID_HIP(h, hipMalloc(&h->d_out, (size_t)KID_NOUT * h->ncell * sizeof(double)));
-  KID_HIP(h, hipMemset(h->d_out, 0, (size_t)KID_NOUT * h->ncell * sizeof(double)));
-  KID_HIP(h, hipMalloc(&h->d_totals, KID_NSCALAR * sizeof(double)));
-  KID_HIP(h, hipMemset(h->d_totals, 0, KID_NSCALAR * sizeof(double)));
-  for (int f = 0; f < KID_NB_F64; ++f) { KID_HIP(h, hipMalloc(&h->bp.f[f], (size_t)capacity * sizeof(double))); KID_HIP(h, hipMemset(h->bp.f[f], 0, (size_t)capacity * sizeof(double))); }
-  for (int f = 0; f < KID_NB_I32; ++f) { KID_HIP(h, hipMalloc(&h->bp.i[f], (size_t)capacity * sizeof(int32_t))); KID_HIP(h, hipMemset(h->bp.i[f], 0, (size_t)capacity * sizeof(int32_t))); }
-  KID_HIP(h, hipMalloc(&h->bp.id, (size_t)capacity * sizeof(int64_t)));
-  KID_HIP(h, hipMemset(h->bp.id, 0, (size_t)capacity * sizeof(int64_t)));
-  KID_HIP(h, hipMalloc(&h->d_bp, sizeof(BergPtrs)));
-  KID_HIP(h, hipMalloc(&h->d_rb, sizeof(RebinTab)));
-  KID_HIP(h, hipMalloc(&h->d_params, sizeof(kid_params)));
-  KID_HIP(h, hipMalloc(&h->d_grid, sizeof(DevGrid)));
-  KID_HIP(h, hipMalloc(&h->d_grid2, sizeof(DevGrid)));
-  KID_HIP(h, hipMalloc(&h->d_vel2, h->ncell * sizeof(VelRec)));
-  KID_HIP(h, hipMalloc(&h->d_trc2, h->ncell * sizeof(TrcRec)));
-  for (int q = 0; q < 2; ++q) { KID_HIP(h, hipMalloc(&h->d_pkt[q], (size_t)h->ncell * PK_GSTRIDE * sizeof(double))); KID_HIP(h, hipMemset(h->d_pkt[q], 0, (size_t)h->ncell * PK_GSTRIDE * sizeof(double))); }
-  KID_HIP(h, hipMalloc(&h->d_lane, (size_t)capacity * sizeof(int)));
-  KID_HIP(h, hipMemset(h->d_lane, 0, (size_t)capacity * sizeof(int)));
-  KID_HIP(h, hipEventCreateWithFlags(&h->evC, hipEventDisableTiming)); KID_HIP(h, hipEventCreateWithFlags(&h->evP, hipEventDisableTiming));
-  KID_HIP(h, hipMalloc(&h->d_count, 4 * sizeof(unsigned long long)));
-  KID_HIP(h, hipMalloc(&h->d_iceberg_counter, h->ncell * sizeof(int32_t)));
-  KID_HIP(h, hipMemset(h->d_iceberg_counter, 0, h->ncell * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->d_fl_cursor, sizeof(int)));
-  KID_HIP(h, hipMalloc(&h->d_redo_list, (size_t)capacity * sizeof(int)));
-  KID_HIP(h, hipMalloc(&h->d_redo_count, sizeof(int)));
-  KID_HIP(h, hipMalloc(&h->d_redo_list2, (size_t)capacity * sizeof(int)));
-  KID_HIP(h, hipMalloc(&h->d_redo_count2, 4 * sizeof(int)));
-  KID_HIP(h, hipMemset(h->d_redo_count2, 0, 4 * sizeof(int)));
+  KID_HIP(h, h->mem.dev(h->d_out, (size_t)KID_NOUT * h->ncell, 0));
+  KID_HIP(h, h->mem.dev(h->d_totals, KID_NSCALAR, 0));
+  for (auto &field : h->bp.f) KID_HIP(h, h->mem.dev(field, cap, 0));
+  for (auto &field : h->bp.i) KID_HIP(h, h->mem.dev(field, cap, 0));
+  KID_HIP(h, h->mem.dev(h->bp.id, cap, 0));
+  KID_HIP(h, h->mem.dev(h->d_bp, 1));
+  KID_HIP(h, h->mem.dev(h->d_rb, 1));
+  KID_HIP(h, h->mem.dev(h->d_params, 1));
+  for (DevGrid **q : {&h->d_grid, &h->d_grid2}) KID_HIP(h, h->mem.dev(*q, 1));
+  for (auto &pkt : h->d_pkt) KID_HIP(h, h->mem.dev(pkt, h->ncell * PK_GSTRIDE, 0));
+  KID_HIP(h, h->mem.dev(h->d_lane, cap, 0));
+  KID_HIP(h, h->mem.dev(h->d_count, 4));
+  KID_HIP(h, h->mem.dev(h->d_iceberg_counter, h->ncell, 0));
+  for (int **q : {&h->d_fl_cursor, &h->d_redo_count}) KID_HIP(h, h->mem.dev(*q, 1));
+  for (int **q : {&h->d_redo_list, &h->d_redo_list2}) KID_HIP(h, h->mem.dev(*q, cap));
+  KID_HIP(h, h->mem.dev(h->d_redo_count2, 4, 0));
   for (int part = 0; part < 2; ++part) for (int par = 0; par < 2; ++par) h->d_redo_cnt[part][par] = h->d_redo_count2 + (2 * part + par);
-  for (int q = 0; q < 2; ++q) { KID_HIP(h, hipEventCreateWithFlags(&h->evF[q], hipEventDisableTiming)); KID_HIP(h, hipEventCreateWithFlags(&h->evG[q], hipEventDisableTiming)); }
-  KID_HIP(h, hipEventCreate(&h->ev0)); KID_HIP(h, hipEventCreate(&h->ev1));
-  KID_HIP(h, hipEventCreate(&h->ev2)); KID_HIP(h, hipEventCreate(&h->ev3));
-  // The hipMemset calls above run on the null stream and are asynchronous to the host, while all later work goes to a
-  // non-blocking stream that does not order itself behind the null stream: without this wait a zero-fill could land
-  // after the first upload (seen once as a zeroed `ine` array of a 1-berg population).
-  KID_HIP(h, hipDeviceSynchronize());
+  for (hipEvent_t *e : {&h->evC, &h->evP, &h->evF[0], &h->evF[1], &h->evG[0], &h->evG[1]}) KID_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  for (hipEvent_t *e : {&h->ev0, &h->ev1, &h->ev2, &h->ev3}) KID_HIP(h, hipEventCreate(e));
+  // The zero-fills above are on the handle's own stream.  kid_set_stream may name another one before the first upload,
+  // and that stream does not order itself behind this one: wait here, or a fill could land after the upload (seen once,
+  // with null-stream fills, as a zeroed `ine` array of a 1-berg population).
+  KID_HIP(h, hipStreamSynchronize(h->stream));
   return KID_OK;
 }
 
-static void mts_free(kid_handle *h);
-static void repro_free(kid_handle *h);
 int kid_destroy(kid_handle *h) {
   if (!h) return KID_EINVAL;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  for (auto &k : h->d_static) if (k) (void)hipFree(k);
-  for (auto &k : h->d_forcing) if (k) (void)hipFree(k);
-  if (h->d_ingest_stage) (void)hipFree(h->d_ingest_stage);
-  if (h->d_calv_state) (void)hipFree(h->d_calv_state);
-  if (h->d_calv_scal) (void)hipFree(h->d_calv_scal);
-  if (h->d_calv_part) (void)hipFree(h->d_calv_part);
-  if (h->d_calv_flag) (void)hipFree(h->d_calv_flag);
-  if (h->d_calv_list) (void)hipFree(h->d_calv_list);
-  if (h->calv_host) (void)hipHostFree(h->calv_host);
-  if (h->d_ingest_key) (void)hipFree(h->d_ingest_key);
-  if (h->d_vel) (void)hipFree(h->d_vel);
-  if (h->d_trc) (void)hipFree(h->d_trc);
-  if (h->d_geo) (void)hipFree(h->d_geo);
-  if (h->d_hotok) (void)hipFree(h->d_hotok);
-  if (h->d_latref) (void)hipFree(h->d_latref);
-  if (h->d_keep) (void)hipFree(h->d_keep);
-  if (h->d_acc_own) (void)hipFree(h->d_acc_own);
-  if (h->d_out) (void)hipFree(h->d_out);
-  if (h->d_totals) (void)hipFree(h->d_totals);
-  for (auto &k : h->bp.f) if (k) (void)hipFree(k);
-  for (auto &k : h->bp.i) if (k) (void)hipFree(k);
-  if (h->bp.id) (void)hipFree(h->bp.id);
-  if (h->d_spare_f64) (void)hipFree(h->d_spare_f64);
-  if (h->d_pos) (void)hipFree(h->d_pos);
-  if (h->d_flag) (void)hipFree(h->d_flag);
-  if (h->d_scan_tmp) (void)hipFree(h->d_scan_tmp);
-  if (h->d_count) (void)hipFree(h->d_count);
-  if (h->d_bp) (void)hipFree(h->d_bp);
-  if (h->d_rb) (void)hipFree(h->d_rb);
-  if (h->d_params) (void)hipFree(h->d_params);
-  if (h->d_grid) (void)hipFree(h->d_grid);
-  if (h->d_grid2) (void)hipFree(h->d_grid2);
-  if (h->d_vel2) (void)hipFree(h->d_vel2);
-  if (h->d_trc2) (void)hipFree(h->d_trc2);
-  for (int q = 0; q < 2; ++q) if (h->d_pkt[q]) (void)hipFree(h->d_pkt[q]);
-  if (h->d_lane) (void)hipFree(h->d_lane);
-  if (h->d_lane_alt) (void)hipFree(h->d_lane_alt);
-  if (h->d_spread_mass_old_own) (void)hipFree(h->d_spread_mass_old_own);
-  for (auto &q : h->d_traj_f) if (q) (void)hipFree(q);
-  if (h->d_traj_day) (void)hipFree(h->d_traj_day);
-  if (h->d_traj_id) (void)hipFree(h->d_traj_id);
-  if (h->d_traj_year) (void)hipFree(h->d_traj_year);
-  if (h->d_traj_nbonds) (void)hipFree(h->d_traj_nbonds);
-  if (h->d_traj_cursor) (void)hipFree(h->d_traj_cursor);
-  if (h->d_mig_buf) (void)hipHostFree(h->d_mig_buf);
-  if (h->mig_word) (void)hipHostFree(h->mig_word);
-  if (h->halo_buf) (void)hipHostFree(h->halo_buf);
-  for (auto &q : h->d_btraj_f) if (q) (void)hipFree(q);
-  for (int f = 0; f < 2; ++f) { if (h->d_btraj_id[f]) (void)hipFree(h->d_btraj_id[f]); if (h->d_btraj_i[f]) (void)hipFree(h->d_btraj_i[f]); }
-  if (h->evR) (void)hipEventDestroy(h->evR);
-  if (h->evC) (void)hipEventDestroy(h->evC);
-  if (h->evP) (void)hipEventDestroy(h->evP);
-  for (int q = 0; q < 2; ++q) { if (h->d_key[q]) (void)hipFree(h->d_key[q]); if (h->d_idx[q]) (void)hipFree(h->d_idx[q]); }
-  if (h->d_sort_tmp) (void)hipFree(h->d_sort_tmp);
-  if (h->d_perm_spare) (void)hipFree(h->d_perm_spare);
-  for (auto &q : h->bp_alt.f) if (q) (void)hipFree(q);
-  for (auto &q : h->bp_alt.i) if (q) (void)hipFree(q);
-  if (h->bp_alt.id) (void)hipFree(h->bp_alt.id);
-  if (h->d_cell_hist) (void)hipFree(h->d_cell_hist);
-  if (h->d_cscan_tmp) (void)hipFree(h->d_cscan_tmp);
-  if (h->d_iceberg_counter) (void)hipFree(h->d_iceberg_counter);
-  if (h->d_fl_cursor) (void)hipFree(h->d_fl_cursor);
-  if (h->d_fl_head) (void)hipFree(h->d_fl_head);
-  if (h->d_fl_next) (void)hipFree(h->d_fl_next);
-  if (h->d_fl_newid) (void)hipFree(h->d_fl_newid);
-  mts_free(h);
-  repro_free(h);
-  if (h->d_budget) (void)hipFree(h->d_budget);
-  if (h->d_budget_plane) (void)hipFree(h->d_budget_plane);
-  if (h->d_orient) (void)hipFree(h->d_orient);
-  if (h->d_redo_list) (void)hipFree(h->d_redo_list);
-  if (h->d_redo_count) (void)hipFree(h->d_redo_count);
-  if (h->d_redo_list2) (void)hipFree(h->d_redo_list2);
-  if (h->d_redo_count2) (void)hipFree(h->d_redo_count2);
-  for (int q = 0; q < 2; ++q) { if (h->evF[q]) (void)hipEventDestroy(h->evF[q]); if (h->evG[q]) (void)hipEventDestroy(h->evG[q]); }
+  if (h->sub_graph_exec) (void)hipGraphExecDestroy(h->sub_graph_exec);
+  for (hipEvent_t e : {h->evR, h->evC, h->evP, h->evF[0], h->evF[1], h->evG[0], h->evG[1], h->ev0, h->ev1, h->ev2, h->ev3}) if (e) (void)hipEventDestroy(e);
   for (auto &pe : h->pending) { (void)hipEventDestroy(pe.first); (void)hipEventDestroy(pe.second); }
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->ev2) (void)hipEventDestroy(h->ev2);
-  if (h->ev3) (void)hipEventDestroy(h->ev3);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+  const int e_rp = h->rp_mem.free_all(), e_mem = h->mem.free_all();
+  const hipError_t e = (hipError_t)(e_rp ? e_rp : e_mem);
   delete h;
+  if (e == hipSuccess) return KID_OK;
+  destroy_err = std::string("kid_destroy: freeing the handle's memory: ") + hipGetErrorString(e);
+  return KID_EHIP;
+}
+
+int kid_memory_in_use(int64_t *device_bytes, int64_t *pinned_bytes) {
+  if (device_bytes) *device_bytes = kid::mem_in_use(kid::MEM_DEVICE).load();
+  if (pinned_bytes) *pinned_bytes = kid::mem_in_use(kid::MEM_PINNED).load();
   return KID_OK;
 }
 
@@ -814,8 +611,6 @@ int kid_set_params(kid_handle *h, const kid_params *params) {
   if (!h->params.old_interp_flds_order && !h->env_off_requested) h->flags.store_env = 1;  // the stored environment is an input again
   return KID_OK;
 }
-static int refresh_tables(kid_handle *h);
-static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one)
 // order the main stream behind general-build launches that are still in flight on the side stream
 static int join_side(kid_handle *h) {
   for (int q = 0; q < 2; ++q)
@@ -861,7 +656,6 @@ int kid_set_stream(kid_handle *h, void *s) {
 // the cell hash of a berg id (ij_component_of_id FW:4227-4240) on this grid: i + iNg * (j - 1) + ij0 with local i, j
 static inline int id_iNg(const kid_grid_desc &d) { return d.gni > 0 ? d.gni : d.iec - d.isc + 1; }
 static inline int id_ij0(const kid_grid_desc &d) { return d.gni > 0 ? d.gi0 + d.gni * d.gj0 : 0; }
-static int mts_check_timeout(kid_handle *h);   // kid_mts_host.inc
 int kid_sync(kid_handle *h) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
@@ -1044,7 +838,7 @@ int kid_download_bergs(kid_handle *h, kid_berg_soa *host) {
 static int layout_flags(kid_handle *h, const int32_t **flags) {
   *flags = h->bp.i[KID_BI_ALIVE];
   if (!h->mig_mode || h->n == 0) return KID_OK;
-  if (!h->d_keep) KID_HIP(h, hipMalloc(&h->d_keep, (size_t)h->capacity * sizeof(int32_t)));
+  if (!h->d_keep) KID_HIP(h, h->mem.dev(h->d_keep, (size_t)h->capacity));
   const KeepSel ks{h->gd.isc, h->gd.iec, h->gd.jsc, h->gd.jec, h->flags.has_static ? h->bp.f[KID_B_HALO_BERG] : nullptr};
   hipLaunchKernelGGL(keep_flags_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->bp.i[KID_BI_ALIVE], h->bp.i[KID_BI_INE], h->bp.i[KID_BI_JNE], ks, h->d_keep, (long long)h->n);
   KID_HIP(h, hipGetLastError());
@@ -1092,19 +886,17 @@ int kid_compact_bergs(kid_handle *h) {
   const long long n = h->n;
   const unsigned nb = (unsigned)((n + 255) / 256);
   if (!h->d_spare_f64) {
-    KID_HIP(h, hipMalloc(&h->d_spare_f64, (size_t)h->capacity * sizeof(double)));
-    KID_HIP(h, hipMalloc(&h->d_pos, (size_t)h->capacity * sizeof(unsigned)));
-    KID_HIP(h, hipMalloc(&h->d_flag, (size_t)h->capacity * sizeof(unsigned)));
+    KID_HIP(h, h->mem.dev(h->d_spare_f64, (size_t)h->capacity));
+    for (unsigned **q : {&h->d_pos, &h->d_flag}) KID_HIP(h, h->mem.dev(*q, (size_t)h->capacity));
     size_t tmp = 0;
     KID_HIP(h, rocprim::exclusive_scan(nullptr, tmp, h->d_flag, h->d_pos, 0u, (size_t)h->capacity, rocprim::plus<unsigned>(), h->stream));
-    h->scan_tmp_bytes = tmp;
-    KID_HIP(h, hipMalloc(&h->d_scan_tmp, tmp));
+    KID_HIP(h, h->mem.reserve(h->scan_tmp, tmp));
   }
   const int32_t *live = nullptr;   // alive, or alive + waiting to be packed (decomposed runs)
   { const int rc_l = layout_flags(h, &live); if (rc_l) return rc_l; }
   hipLaunchKernelGGL(alive_to_u32_kernel, dim3(nb), dim3(256), 0, h->stream, live, h->d_flag, n);
-  size_t tmp = h->scan_tmp_bytes;
-  KID_HIP(h, rocprim::exclusive_scan(h->d_scan_tmp, tmp, h->d_flag, h->d_pos, 0u, (size_t)n, rocprim::plus<unsigned>(), h->stream));
+  size_t tmp = h->scan_tmp.bytes;
+  KID_HIP(h, rocprim::exclusive_scan(h->scan_tmp.p, tmp, h->d_flag, h->d_pos, 0u, (size_t)n, rocprim::plus<unsigned>(), h->stream));
   int64_t n_alive = 0;
   // (the count of rows that stay)
   {
@@ -1171,11 +963,6 @@ static bool field_never_written(const kid_handle *h, int f) {
 // environment selects a stable comparison sort instead.
 // Correctness never depends on it (the kernels accept any order); speed does: the hot build shares LDS cell
 // packets and atomics between the lanes of a wave that sit in the same cell.
-static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count);
-static int rebin_plan(kid_handle *h);
-static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);
-static bool plain_namelist(const kid_handle *h);
-static bool lanes_eligible(const kid_handle *h);
 // Is a step of this handle ONE plain hot build over the whole population (kid_step_local's last branch -> launch_berg with
 // evolve | thermo | spread)?  Only then can the copy of a re-binning wait for the step: asked when the re-binning is planned,
 // at the head of kid_step_local and by launch_berg itself.  The slow-lane schedule (it re-bins inside the step, with the
@@ -1218,22 +1005,17 @@ static int rebin_plan(kid_handle *h) {
   const unsigned dead_key = (unsigned)h->ncell;  // larger than any cell index
   if (!h->d_key[0]) {
     h->stable_resort = h->dbg.stable_resort;  // a stable comparison sort keeps the row order inside a cell
-    for (int q = 0; q < 2; ++q) {
-      KID_HIP(h, hipMalloc(&h->d_key[q], (size_t)h->capacity * sizeof(unsigned)));
-      KID_HIP(h, hipMalloc(&h->d_idx[q], (size_t)h->capacity * sizeof(unsigned)));
-    }
+    for (unsigned **q : {&h->d_key[0], &h->d_key[1], &h->d_idx[0], &h->d_idx[1]}) KID_HIP(h, h->mem.dev(*q, (size_t)h->capacity));
     size_t tmp = 0;
     KID_HIP(h, rocprim::radix_sort_pairs(nullptr, tmp, h->d_key[0], h->d_key[1], h->d_idx[0], h->d_idx[1], (size_t)h->capacity, 0u, 32u, h->stream));
-    h->sort_tmp_bytes = tmp;
-    KID_HIP(h, hipMalloc(&h->d_sort_tmp, tmp));
-    KID_HIP(h, hipMalloc(&h->d_cell_hist, ((size_t)h->ncell + 1) * sizeof(unsigned)));
+    KID_HIP(h, h->mem.reserve(h->sort_tmp, tmp));
+    KID_HIP(h, h->mem.dev(h->d_cell_hist, (size_t)h->ncell + 1));
     tmp = 0;
     KID_HIP(h, rocprim::exclusive_scan(nullptr, tmp, h->d_cell_hist, h->d_cell_hist, 0u, (size_t)h->ncell + 1, rocprim::plus<unsigned>(), h->stream));
-    h->cscan_tmp_bytes = tmp;
-    KID_HIP(h, hipMalloc(&h->d_cscan_tmp, tmp ? tmp : 8));
-    for (int f = 0; f < KID_NB_F64; ++f) KID_HIP(h, hipMalloc(&h->bp_alt.f[f], (size_t)h->capacity * sizeof(double)));
-    for (int f = 0; f < KID_NB_I32; ++f) KID_HIP(h, hipMalloc(&h->bp_alt.i[f], (size_t)h->capacity * sizeof(int32_t)));
-    KID_HIP(h, hipMalloc(&h->bp_alt.id, (size_t)h->capacity * sizeof(int64_t)));
+    KID_HIP(h, h->mem.reserve(h->cscan_tmp, tmp));
+    for (auto &field : h->bp_alt.f) KID_HIP(h, h->mem.dev(field, (size_t)h->capacity));
+    for (auto &field : h->bp_alt.i) KID_HIP(h, h->mem.dev(field, (size_t)h->capacity));
+    KID_HIP(h, h->mem.dev(h->bp_alt.id, (size_t)h->capacity));
   }
   const int32_t *live = nullptr;   // alive, or alive + waiting to be packed (decomposed runs): those keep their cell as key
   { const int rc_l = layout_flags(h, &live); if (rc_l) return rc_l; }
@@ -1242,15 +1024,15 @@ static int rebin_plan(kid_handle *h) {
     unsigned bits = 1; while ((1ull << bits) <= (unsigned long long)dead_key) ++bits;
     hipLaunchKernelGGL(cell_key_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.i[KID_BI_INE], h->bp.i[KID_BI_JNE], live,
                        h->gd.isd, h->gd.jsd, h->ni, dead_key, h->d_key[0], h->d_idx[0], n);
-    size_t tmp = h->sort_tmp_bytes;
-    KID_HIP(h, rocprim::radix_sort_pairs(h->d_sort_tmp, tmp, h->d_key[0], h->d_key[1], h->d_idx[0], h->d_idx[1], (size_t)n, 0u, bits, h->stream));
+    size_t tmp = h->sort_tmp.bytes;
+    KID_HIP(h, rocprim::radix_sort_pairs(h->sort_tmp.p, tmp, h->d_key[0], h->d_key[1], h->d_idx[0], h->d_idx[1], (size_t)n, 0u, bits, h->stream));
     perm = h->d_idx[1];
   } else {
     KID_HIP(h, hipMemsetAsync(h->d_cell_hist, 0, ((size_t)h->ncell + 1) * sizeof(unsigned), h->stream));
     hipLaunchKernelGGL(cell_rank_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.i[KID_BI_INE], h->bp.i[KID_BI_JNE], live,
                        h->gd.isd, h->gd.jsd, h->ni, dead_key, h->d_key[0], h->d_key[1], h->d_cell_hist, n);
-    size_t tmp = h->cscan_tmp_bytes;
-    KID_HIP(h, rocprim::exclusive_scan(h->d_cscan_tmp, tmp, h->d_cell_hist, h->d_cell_hist, 0u, (size_t)h->ncell + 1, rocprim::plus<unsigned>(), h->stream));
+    size_t tmp = h->cscan_tmp.bytes;
+    KID_HIP(h, rocprim::exclusive_scan(h->cscan_tmp.p, tmp, h->d_cell_hist, h->d_cell_hist, 0u, (size_t)h->ncell + 1, rocprim::plus<unsigned>(), h->stream));
     hipLaunchKernelGGL(cell_place_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_key[0], h->d_key[1], h->d_cell_hist, h->d_idx[1], h->d_idx[0], n);
     perm = h->d_idx[1];
     if (carry_repro) { hipLaunchKernelGGL(translate_rows_kernel, dim3(nb), dim3(256), 0, h->stream, h->rp.srows, (const unsigned *)h->d_idx[0], n); h->rp.srows_n = n; }
@@ -1288,7 +1070,7 @@ static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list
   const unsigned nb = (unsigned)((n + 255) / 256);
   if (with_lane) {
     if (h->stable_resort) { h->err = "KID_STABLE_RESORT has no inverse permutation for the slow-lane re-binning"; return KID_EUNSUPPORTED; }
-    if (!h->d_lane_alt) { KID_HIP(h, hipMalloc(&h->d_lane_alt, (size_t)h->capacity * sizeof(int))); KID_HIP(h, hipMemsetAsync(h->d_lane_alt, 0, (size_t)h->capacity * sizeof(int), h->stream)); }
+    if (!h->d_lane_alt) KID_HIP(h, h->mem.dev(h->d_lane_alt, (size_t)h->capacity, 0));
     t.src[t.n8 + t.n4] = h->d_lane; t.dst[t.n8 + t.n4] = h->d_lane_alt; ++t.n4;
   }
   hipLaunchKernelGGL(permute_all_kernel, dim3(nb), dim3(256), 0, h->stream, t, h->rplan.perm, n);
@@ -1360,7 +1142,6 @@ int kid_zero_accumulators(kid_handle *h) {
 
 }  // extern "C"
 
-static int refresh_tables(kid_handle *h);
 // May the hot build be the plain one (berg_kernel<..., K = 1>, kid_device.hpp)?  Only when every switch of KID_SWITCHES
 // has the value that build folds in, and none of the handle's flags is set.
 static bool plain_namelist(const kid_handle *h) {
@@ -1391,8 +1172,6 @@ static void launch_stage(kid_handle *h, unsigned nbp, const DevGrid *gtab, const
     hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false, 0, true>), dim3((unsigned)std::min<long long>((klen + 63) / 64, 2048)), dim3(64), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);
   }
 }
-static int repro_refuse(kid_handle *h);
-static int repro_fold(kid_handle *h, bool thermo, bool spread, long long k0, long long klen);
 template <unsigned PH>
 static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_len = -1) {   // range: the rows to step (default all)
   if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
@@ -1573,8 +1352,6 @@ static int launch_berg_lanes(kid_handle *h) {
 
 extern "C" {
 
-static int mts_depth(kid_handle *h);
-static int bond_orientations(kid_handle *h);
 int kid_evolve_icebergs_mts(kid_handle *h);
 int kid_evolve_icebergs_interactive(kid_handle *h);
 int kid_interp_gridded_fields_to_bergs(kid_handle *h) {
@@ -1640,16 +1417,13 @@ static int fl_place_children(kid_handle *h, long long n_old, int m, unsigned ste
 }
 static int fl_assign_ids(kid_handle *h, long long n_old, int m) {
   if (m <= 0) return KID_OK;
-  if (!h->d_fl_head) {
-    KID_HIP(h, hipMalloc(&h->d_fl_head, h->ncell * sizeof(int32_t)));
-    KID_HIP(h, hipMemsetAsync(h->d_fl_head, 0xff, h->ncell * sizeof(int32_t), h->stream));   // -1: empty lists
-  }
+  if (!h->d_fl_head) KID_HIP(h, h->mem.dev(h->d_fl_head, h->ncell, 0xff));   // -1: empty lists
   if (m > h->fl_ev_capacity) {
-    if (h->d_fl_next) (void)hipFree(h->d_fl_next);
-    if (h->d_fl_newid) (void)hipFree(h->d_fl_newid);
+    KID_HIP(h, h->mem.drop(h->d_fl_next));
+    KID_HIP(h, h->mem.drop(h->d_fl_newid));
     h->fl_ev_capacity = std::max<long long>(2ll * m, 4096);
-    KID_HIP(h, hipMalloc(&h->d_fl_next, (size_t)h->fl_ev_capacity * sizeof(int32_t)));
-    KID_HIP(h, hipMalloc(&h->d_fl_newid, (size_t)h->fl_ev_capacity * sizeof(int64_t)));
+    KID_HIP(h, h->mem.dev(h->d_fl_next, (size_t)h->fl_ev_capacity));
+    KID_HIP(h, h->mem.dev(h->d_fl_newid, (size_t)h->fl_ev_capacity));
   }
   const FlIdCtx x{h->d_fl_head, h->d_fl_next, h->d_fl_newid, h->d_iceberg_counter, n_old, m, id_iNg(h->gd), id_ij0(h->gd)};
   const dim3 grid((unsigned)((m + 255) / 256)), block(256);
@@ -1822,8 +1596,7 @@ int kid_step_local(kid_handle *h) {
     // gather into grd%spread_mass_old, planes reset), then thermodynamics + create_gridded_icebergs_fields as usual; the
     // gather replaces floating_melt by (spread_mass_old - spread_mass)/dt (IB:3436-3445)
     if (!h->d_spread_mass_old) {
-      KID_HIP(h, hipMalloc(&h->d_spread_mass_old_own, 2 * h->ncell * sizeof(double)));   // + spread_mass_tmp
-      KID_HIP(h, hipMemsetAsync(h->d_spread_mass_old_own, 0, 2 * h->ncell * sizeof(double), h->stream));
+      KID_HIP(h, h->mem.dev(h->d_spread_mass_old_own, 2 * h->ncell, 0));   // + spread_mass_tmp
       h->d_spread_mass_old = h->d_spread_mass_old_own;
     }
     if (!p.static_icebergs) { rc = p.old_interp_flds_order ? launch_berg<PH_EVOLVE>(h) : launch_berg<PH_INTERP | PH_EVOLVE>(h); if (rc) return rc; }

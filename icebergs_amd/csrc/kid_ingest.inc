@@ -131,15 +131,20 @@ __global__ void __launch_bounds__(256) ingest_scrub_kernel(IngestArgs a) {  // I
   }
 }
 
+// host arrays pass through one device block, shared with kid_calving; a kernel may still read the block it outgrows
+static int ingest_stage_reserve(kid_handle *h, size_t count) {
+  if (count <= h->ingest_stage_count) return KID_OK;
+  if (h->d_ingest_stage) { KID_HIP(h, hipStreamSynchronize(h->stream)); KID_HIP(h, h->mem.drop(h->d_ingest_stage)); }
+  h->ingest_stage_count = 0;
+  KID_HIP(h, h->mem.dev(h->d_ingest_stage, count));
+  h->ingest_stage_count = count;
+  return KID_OK;
+}
 static int ingest_stage(kid_handle *h, const kid_forcing_in *in, const size_t cnt[11], const double *src[11], const double *dev[11]) {
   size_t total = 0;
   for (int k = 0; k < 11; ++k) total += src[k] ? cnt[k] : 0;
   if (in->on_device) { for (int k = 0; k < 11; ++k) dev[k] = src[k]; return KID_OK; }
-  if (total > h->ingest_stage_count) {
-    if (h->d_ingest_stage) { KID_HIP(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->d_ingest_stage); h->d_ingest_stage = nullptr; }
-    KID_HIP(h, hipMalloc(&h->d_ingest_stage, total * sizeof(double)));
-    h->ingest_stage_count = total;
-  }
+  { const int rc = ingest_stage_reserve(h, total); if (rc) return rc; }
   size_t off = 0;
   for (int k = 0; k < 11; ++k) {
     if (!src[k]) { dev[k] = nullptr; continue; }
@@ -197,7 +202,7 @@ int kid_ingest_forcing(kid_handle *h, const kid_forcing_in *in) {
   a.ssh = dev[6]; a.sst = dev[7]; a.cn = dev[8]; a.hi = dev[9]; a.sss = dev[10];
   for (int k = 0; k < KID_NFORCING; ++k) a.out[k] = h->d_forcing[k];
   a.msk = h->d_static[KID_G_MSK];
-  if (!h->d_ingest_key) KID_HIP(h, hipMalloc(&h->d_ingest_key, sizeof(unsigned long long)));
+  if (!h->d_ingest_key) KID_HIP(h, h->mem.dev(h->d_ingest_key, 1));
   a.sstmax_key = h->d_ingest_key;
   KID_HIP(h, hipMemsetAsync(h->d_ingest_key, 0, sizeof(unsigned long long), h->stream));
   const int nb_c = std::min(njc, 512), nb = (int)((h->ncell + 255) / 256);

@@ -118,7 +118,6 @@ __global__ void __launch_bounds__(64) unpack_immigrants_kernel(const DevGrid g, 
 
 extern "C" {
 
-static int halo_bergs_supported(kid_handle *h, const char *what);   // kid_halo_bergs.inc
 static int mig_supported(kid_handle *h) {
   h->mig_mode = true;   // from the first migration call on, dead rows waiting to be packed survive tail drops, compaction and re-binning (layout_flags)
   if (h->have_bonds || h->params.iceberg_bonds_on || h->params.mts || h->params.dem) {
@@ -136,13 +135,13 @@ int kid_buffer_width(kid_handle *h, int32_t *width) {
 
 static unsigned long long *mig_pinned_word(kid_handle *h) { return h->mig_word; }   // where the one host read of a call lands (two counters)
 static int mig_stage(kid_handle *h, long long rows) {   // host-visible staging the device reads and writes directly (pinned, grows)
-  if (!h->mig_word) KID_HIP(h, hipHostMalloc((void **)&h->mig_word, 2 * sizeof(unsigned long long)));
+  if (!h->mig_word) KID_HIP(h, h->mem.pinned(h->mig_word, 2));
   if (rows <= h->mig_capacity) return KID_OK;
   KID_HIP(h, hipStreamSynchronize(h->stream));
-  if (h->d_mig_buf) (void)hipHostFree(h->d_mig_buf);
-  h->d_mig_buf = nullptr; h->mig_capacity = 0;
+  h->mig_capacity = 0;
+  KID_HIP(h, h->mem.drop(h->d_mig_buf));
   const long long cap = std::max<long long>(rows, 4096);
-  KID_HIP(h, hipHostMalloc((void **)&h->d_mig_buf, (size_t)cap * MIG_WIDTH * sizeof(double)));
+  KID_HIP(h, h->mem.pinned(h->d_mig_buf, (size_t)cap * MIG_WIDTH));
   h->mig_capacity = cap;
   return KID_OK;
 }

@@ -6,56 +6,33 @@ static int mts_ensure(kid_handle *h, int mb) {
   if (h->mts_ready && h->mb == mb) return KID_OK;
   if (h->mts_ready) { h->err = "max_bonds cannot change after the bond tables exist"; return KID_EINVAL; }
   const size_t cap = (size_t)h->capacity, nb = (size_t)(mb > 0 ? mb : 1) * cap;
-  KID_HIP(h, hipMalloc(&h->mts.bcount, cap * sizeof(int32_t)));      KID_HIP(h, hipMemset(h->mts.bcount, 0, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.bother_id, nb * sizeof(int64_t)));    KID_HIP(h, hipMemset(h->mts.bother_id, 0, nb * sizeof(int64_t)));
-  KID_HIP(h, hipMalloc(&h->mts.bbroken, nb * sizeof(int32_t)));      KID_HIP(h, hipMemset(h->mts.bbroken, 0, nb * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.bother_row, nb * sizeof(int32_t)));   KID_HIP(h, hipMemset(h->mts.bother_row, 0xff, nb * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.bother_slot, nb * sizeof(int32_t)));  KID_HIP(h, hipMemset(h->mts.bother_slot, 0xff, nb * sizeof(int32_t)));
-  for (int f = 0; f < KID_NBOND_F64; ++f) { KID_HIP(h, hipMalloc(&h->mts.bf[f], nb * sizeof(double))); KID_HIP(h, hipMemset(h->mts.bf[f], 0, nb * sizeof(double))); }
-  KID_HIP(h, hipMalloc(&h->mts.rank, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.order, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.cell_start, (h->ncell + 2) * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.cell_conglom, (h->ncell + 2) * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.label, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.root_flag, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.root_scan, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->mts.red, MR_COUNT * sizeof(double)));     KID_HIP(h, hipMemset(h->mts.red, 0, MR_COUNT * sizeof(double)));
-  KID_HIP(h, hipMalloc(&h->mts.rec, 3 * 8 * cap * sizeof(double)));  KID_HIP(h, hipMemset(h->mts.rec, 0, 3 * 8 * cap * sizeof(double)));
-  for (int q = 0; q < 2; ++q) { KID_HIP(h, hipMalloc(&h->d_key64[q], cap * sizeof(unsigned long long))); KID_HIP(h, hipMalloc(&h->d_rows[q], cap * sizeof(int))); }
-  KID_HIP(h, hipMalloc(&h->d_last_key, cap * sizeof(unsigned long long))); KID_HIP(h, hipMalloc(&h->d_order_flag, 4 * sizeof(int))); KID_HIP(h, hipMemset(h->d_order_flag, 0, 4 * sizeof(int)));   // [0] order changed, [1] bond lists changed, [2] lanes of the fused sub-step kernel that timed out
-  KID_HIP(h, hipMalloc(&h->d_bond_sig, cap * sizeof(unsigned long long))); KID_HIP(h, hipMemset(h->d_bond_sig, 0, cap * sizeof(unsigned long long)));
+  KID_HIP(h, h->mem.dev(h->mts.bcount, cap, 0));
+  KID_HIP(h, h->mem.dev(h->mts.bother_id, nb, 0));
+  KID_HIP(h, h->mem.dev(h->mts.bbroken, nb, 0));
+  for (int32_t **q : {&h->mts.bother_row, &h->mts.bother_slot}) KID_HIP(h, h->mem.dev(*q, nb, 0xff));   // -1: no partner row known
+  for (auto &field : h->mts.bf) KID_HIP(h, h->mem.dev(field, nb, 0));
+  for (int32_t **q : {&h->mts.rank, &h->mts.order, &h->mts.label, &h->mts.root_flag, &h->mts.root_scan}) KID_HIP(h, h->mem.dev(*q, cap));
+  for (int32_t **q : {&h->mts.cell_start, &h->mts.cell_conglom}) KID_HIP(h, h->mem.dev(*q, h->ncell + 2));
+  KID_HIP(h, h->mem.dev(h->mts.red, MR_COUNT, 0));
+  KID_HIP(h, h->mem.dev(h->mts.rec, 3 * 8 * cap, 0));
+  for (int q = 0; q < 2; ++q) { KID_HIP(h, h->mem.dev(h->d_key64[q], cap)); KID_HIP(h, h->mem.dev(h->d_rows[q], cap)); }
+  KID_HIP(h, h->mem.dev(h->d_last_key, cap)); KID_HIP(h, h->mem.dev(h->d_order_flag, 4, 0));   // [0] order changed, [1] bond lists changed, [2] lanes of the fused sub-step kernel that timed out
+  KID_HIP(h, h->mem.dev(h->d_bond_sig, cap, 0));
   h->order_n = -1; h->mts_shadow_valid = false; h->labels_stale = true;
   size_t b1 = 0, b2 = 0;
   KID_HIP(h, rocprim::radix_sort_pairs(nullptr, b1, h->d_key64[0], h->d_key64[1], h->d_rows[0], h->d_rows[1], cap, 0, 64, h->stream));
   KID_HIP(h, rocprim::exclusive_scan(nullptr, b2, h->mts.root_flag, h->mts.root_scan, 0, cap, rocprim::plus<int>(), h->stream));
-  h->mts_tmp_bytes = b1 > b2 ? b1 : b2;
-  KID_HIP(h, hipMalloc(&h->d_mts_tmp, h->mts_tmp_bytes));
-  KID_HIP(h, hipMalloc(&h->d_mts, sizeof(MtsDev)));
+  KID_HIP(h, h->mem.reserve(h->mts_tmp, b1 > b2 ? b1 : b2));
+  KID_HIP(h, h->mem.dev(h->d_mts, 1));
   h->mts.stride = (long long)h->capacity; h->mts.mb = mb; h->mts.nperm = 0;
   h->mts.lonc = h->d_static[KID_G_LONC]; h->mts.latc = h->d_static[KID_G_LATC]; h->mts.glon = h->d_static[KID_G_LON];
   h->mb = mb; h->mts_ready = true; h->mts_dirty = true;
-  KID_HIP(h, hipDeviceSynchronize());  // null-stream fills above vs the handle's non-blocking stream (see kid_create)
+  KID_HIP(h, hipStreamSynchronize(h->stream));  // the fills above, before a launch on another stream could read the tables
   return KID_OK;
 }
 // the tables with the namelist's max_bonds slots (at least one), unless they exist already
 static int mts_ensure_default(kid_handle *h) {
   return h->mts_ready ? KID_OK : mts_ensure(h, h->params.max_bonds > 0 ? h->params.max_bonds : 1);
-}
-static void mts_free(kid_handle *h) {
-  if (h->sub_graph_exec) { (void)hipGraphExecDestroy(h->sub_graph_exec); h->sub_graph_exec = nullptr; }
-  if (!h->mts_ready) return;
-  (void)hipFree(h->mts.bcount); (void)hipFree(h->mts.bother_id); (void)hipFree(h->mts.bbroken); (void)hipFree(h->mts.bother_row); (void)hipFree(h->mts.bother_slot);
-  for (int f = 0; f < KID_NBOND_F64; ++f) (void)hipFree(h->mts.bf[f]);
-  (void)hipFree(h->mts.rank); (void)hipFree(h->mts.order); (void)hipFree(h->mts.cell_start); (void)hipFree(h->mts.cell_conglom); (void)hipFree(h->mts.label);
-  (void)hipFree(h->mts.root_flag); (void)hipFree(h->mts.root_scan); (void)hipFree(h->mts.red);
-  (void)hipFree(h->mts.rec);
-  for (int q = 0; q < 2; ++q) { (void)hipFree(h->d_key64[q]); (void)hipFree(h->d_rows[q]); }
-  (void)hipFree(h->d_last_key); (void)hipFree(h->d_order_flag); (void)hipFree(h->d_bond_sig); h->d_last_key = nullptr; h->d_order_flag = nullptr; h->d_bond_sig = nullptr;
-  h->order_n = -1; h->mts_shadow_valid = false; h->labels_stale = true;
-  (void)hipFree(h->d_mts_tmp); (void)hipFree(h->d_mts);
-  if (h->d_bond_words) { (void)hipFree(h->d_bond_words); h->d_bond_words = nullptr; }
-  if (h->d_static_rows) { (void)hipFree(h->d_static_rows); h->d_static_rows = nullptr; h->static_rows_n = -1; }
-  h->mts_ready = false;
 }
 static int mts_refresh(kid_handle *h) {  // derived constants + the device copy of the table
   int rc = refresh_tables(h);
@@ -191,15 +168,15 @@ static int mts_build_order(kid_handle *h) {
   h->labels_stale = true;
   h->order_n = -1;
   if (!h->d_static_rows || h->static_rows_n != n) {
-    if (h->d_static_rows && h->static_rows_cap < n) { (void)hipFree(h->d_static_rows); h->d_static_rows = nullptr; }
-    if (!h->d_static_rows) { KID_HIP(h, hipMalloc(&h->d_static_rows, (size_t)h->capacity * sizeof(int))); h->static_rows_cap = h->capacity; }
+    if (h->static_rows_cap < n) KID_HIP(h, h->mem.drop(h->d_static_rows));
+    if (!h->d_static_rows) { KID_HIP(h, h->mem.dev(h->d_static_rows, (size_t)h->capacity)); h->static_rows_cap = h->capacity; }
     hipLaunchKernelGGL(mts_iota_kernel, MTS_GRID(n), h->d_rows[cur], n);
     const int f64_keys[4] = {KID_B_START_LAT, KID_B_START_LON, KID_B_START_MASS, KID_B_START_DAY};
     for (int pass = 0; pass < 5; ++pass) {
       if (pass < 4) hipLaunchKernelGGL(mts_key_f64_kernel, MTS_GRID(n), (const double *)h->bp.f[f64_keys[pass]], (const int *)h->d_rows[cur], h->d_key64[0], n);
       else hipLaunchKernelGGL(mts_key_i32_kernel, MTS_GRID(n), (const int32_t *)h->bp.i[KID_BI_START_YEAR], (const int *)h->d_rows[cur], h->d_key64[0], n);
-      size_t bytes = h->mts_tmp_bytes;
-      KID_HIP(h, rocprim::radix_sort_pairs(h->d_mts_tmp, bytes, h->d_key64[0], h->d_key64[1], h->d_rows[cur], h->d_rows[cur ^ 1], (size_t)n, 0, 64, h->stream));
+      size_t bytes = h->mts_tmp.bytes;
+      KID_HIP(h, rocprim::radix_sort_pairs(h->mts_tmp.p, bytes, h->d_key64[0], h->d_key64[1], h->d_rows[cur], h->d_rows[cur ^ 1], (size_t)n, 0, 64, h->stream));
       cur ^= 1;
     }
     KID_HIP(h, hipMemcpyAsync(h->d_static_rows, h->d_rows[cur], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -209,8 +186,8 @@ static int mts_build_order(kid_handle *h) {
   KID_HIP(h, hipMemcpyAsync(h->d_rows[cur], h->d_static_rows, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
   {
     hipLaunchKernelGGL(mts_key_cell_kernel, MTS_GRID(n), dev_grid(h), (const BergPtrs *)h->d_bp, (const int *)h->d_rows[cur], h->d_key64[0], h->d_last_key, n);
-    size_t bytes = h->mts_tmp_bytes;
-    KID_HIP(h, rocprim::radix_sort_pairs(h->d_mts_tmp, bytes, h->d_key64[0], h->d_key64[1], h->d_rows[cur], h->d_rows[cur ^ 1], (size_t)n, 0, 64, h->stream));
+    size_t bytes = h->mts_tmp.bytes;
+    KID_HIP(h, rocprim::radix_sort_pairs(h->mts_tmp.p, bytes, h->d_key64[0], h->d_key64[1], h->d_rows[cur], h->d_rows[cur ^ 1], (size_t)n, 0, 64, h->stream));
     cur ^= 1;
   }
   KID_HIP(h, hipMemcpyAsync(h->mts.order, h->d_rows[cur], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -288,8 +265,8 @@ int kid_set_conglom_ids(kid_handle *h) {
   }
   KID_HIP(h, hipMemsetAsync(h->mts.root_flag, 0, (size_t)n * sizeof(int32_t), h->stream));
   hipLaunchKernelGGL(conglom_roots_kernel, MTS_GRID(n), bt, mt, n);
-  size_t bytes = h->mts_tmp_bytes;
-  KID_HIP(h, rocprim::exclusive_scan(h->d_mts_tmp, bytes, h->mts.root_flag, h->mts.root_scan, 0, (size_t)n, rocprim::plus<int>(), h->stream));
+  size_t bytes = h->mts_tmp.bytes;
+  KID_HIP(h, rocprim::exclusive_scan(h->mts_tmp.p, bytes, h->mts.root_flag, h->mts.root_scan, 0, (size_t)n, rocprim::plus<int>(), h->stream));
   hipLaunchKernelGGL(conglom_assign_kernel, MTS_GRID(n), bt, mt, n);
   if (h->params.use_broken_bonds_for_substep_contact && h->have_bonds) {
     hipLaunchKernelGGL(conglom_prune_kernel, MTS_GRID(n), pp, bt, mt, n);
@@ -304,7 +281,6 @@ int kid_set_conglom_ids(kid_handle *h) {
   return KID_OK;
 }
 
-static int mts_fold_scalars(kid_handle *h);
 
 // what kid_evolve_icebergs_mts and kid_evolve_icebergs_interactive do before their sweeps, when there are bergs
 static int mts_prologue(kid_handle *h) {
@@ -546,7 +522,7 @@ static int bond_orientations(kid_handle *h) {
     if (h->bp.orient) { h->bp.orient = nullptr; h->tables_dirty = true; }
     return KID_OK;
   }
-  if (!h->d_orient) KID_HIP(h, hipMalloc(&h->d_orient, (size_t)h->capacity * sizeof(double)));
+  if (!h->d_orient) KID_HIP(h, h->mem.dev(h->d_orient, (size_t)h->capacity));
   int rc = mts_ensure(h, h->mb);
   if (rc) return rc;
   if (h->bp.orient != h->d_orient) { h->bp.orient = h->d_orient; h->tables_dirty = true; }

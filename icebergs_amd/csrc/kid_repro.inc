@@ -156,35 +156,29 @@ __global__ void __launch_bounds__(256) repro_heat_finish_kernel(const double *__
 
 }  // namespace
 
-static void repro_free(kid_handle *h) {
-  for (void *q : {(void *)h->rp.stage, (void *)h->rp.key, (void *)h->rp.mask, (void *)h->rp.srows, (void *)h->rp.k64[0], (void *)h->rp.k64[1],
-                  (void *)h->rp.rows[0], (void *)h->rp.rows[1], (void *)h->rp.k32[0], (void *)h->rp.k32[1], (void *)h->rp.cs, (void *)h->rp.cell_heat,
-                  (void *)h->rp.part, h->rp.tmp})
-    if (q) (void)hipFree(q);
+// switching the mode off returns all of its memory: the mode has an owner of its own
+static int repro_free(kid_handle *h) {
   h->rp = kid_handle::Repro{};
+  KID_HIP(h, (hipError_t)h->rp_mem.free_all());
+  return KID_OK;
 }
 // the buffers of the mode, sized by the handle's capacity and grid (allocated once, when the switch is turned on)
 static int repro_alloc(kid_handle *h) {
   if (h->rp.stage) return KID_OK;
   const size_t cap = (size_t)h->capacity, nc = h->ncell;
   const size_t nparts = (nc + 255) / 256;
-  KID_HIP(h, hipMalloc(&h->rp.stage, (size_t)KID_ST_N * cap * sizeof(double)));
-  KID_HIP(h, hipMalloc(&h->rp.key, cap * sizeof(int32_t)));
-  KID_HIP(h, hipMalloc(&h->rp.mask, cap * sizeof(unsigned long long)));
-  KID_HIP(h, hipMalloc(&h->rp.srows, cap * sizeof(int)));
-  for (int q = 0; q < 2; ++q) {
-    KID_HIP(h, hipMalloc(&h->rp.k64[q], cap * sizeof(unsigned long long)));
-    KID_HIP(h, hipMalloc(&h->rp.rows[q], cap * sizeof(int)));
-    KID_HIP(h, hipMalloc(&h->rp.k32[q], cap * sizeof(unsigned)));
-  }
-  KID_HIP(h, hipMalloc(&h->rp.cs, (nc + 1) * sizeof(int)));
-  KID_HIP(h, hipMalloc(&h->rp.cell_heat, nc * sizeof(double)));
-  KID_HIP(h, hipMalloc(&h->rp.part, nparts * sizeof(double)));
+  KID_HIP(h, h->rp_mem.dev(h->rp.stage, (size_t)KID_ST_N * cap));
+  KID_HIP(h, h->rp_mem.dev(h->rp.key, cap));
+  KID_HIP(h, h->rp_mem.dev(h->rp.mask, cap));
+  KID_HIP(h, h->rp_mem.dev(h->rp.srows, cap));
+  for (int q = 0; q < 2; ++q) { KID_HIP(h, h->rp_mem.dev(h->rp.k64[q], cap)); KID_HIP(h, h->rp_mem.dev(h->rp.rows[q], cap)); KID_HIP(h, h->rp_mem.dev(h->rp.k32[q], cap)); }
+  KID_HIP(h, h->rp_mem.dev(h->rp.cs, nc + 1));
+  KID_HIP(h, h->rp_mem.dev(h->rp.cell_heat, nc));
+  KID_HIP(h, h->rp_mem.dev(h->rp.part, nparts));
   size_t b64 = 0, b32 = 0;
   KID_HIP(h, rocprim::radix_sort_pairs(nullptr, b64, h->rp.k64[0], h->rp.k64[1], h->rp.rows[0], h->rp.rows[1], cap, 0, 64, h->stream));
   KID_HIP(h, rocprim::radix_sort_pairs(nullptr, b32, h->rp.k32[0], h->rp.k32[1], h->rp.rows[0], h->rp.rows[1], cap, 0, 32, h->stream));
-  h->rp.tmp_bytes = std::max(b64, b32);
-  KID_HIP(h, hipMalloc(&h->rp.tmp, h->rp.tmp_bytes));
+  KID_HIP(h, h->rp_mem.reserve(h->rp.tmp, std::max(b64, b32)));
   h->rp.srows_n = -1;
   return KID_OK;
 }
@@ -210,8 +204,8 @@ static int repro_static_order(kid_handle *h) {
     if (pass == 0) hipLaunchKernelGGL(repro_key_id_kernel, grid, block, 0, h->stream, (const int64_t *)h->bp.id, (const int *)h->rp.rows[cur], h->rp.k64[0], n);
     else if (pass < 5) hipLaunchKernelGGL(mts_key_f64_kernel, grid, block, 0, h->stream, (const double *)h->bp.f[f64_keys[pass - 1]], (const int *)h->rp.rows[cur], h->rp.k64[0], n);
     else hipLaunchKernelGGL(mts_key_i32_kernel, grid, block, 0, h->stream, (const int32_t *)h->bp.i[KID_BI_START_YEAR], (const int *)h->rp.rows[cur], h->rp.k64[0], n);
-    size_t bytes = h->rp.tmp_bytes;
-    KID_HIP(h, rocprim::radix_sort_pairs(h->rp.tmp, bytes, h->rp.k64[0], h->rp.k64[1], h->rp.rows[cur], h->rp.rows[cur ^ 1], (size_t)n, 0, 64, h->stream));
+    size_t bytes = h->rp.tmp.bytes;
+    KID_HIP(h, rocprim::radix_sort_pairs(h->rp.tmp.p, bytes, h->rp.k64[0], h->rp.k64[1], h->rp.rows[cur], h->rp.rows[cur ^ 1], (size_t)n, 0, 64, h->stream));
     cur ^= 1;
   }
   KID_HIP(h, hipMemcpyAsync(h->rp.srows, h->rp.rows[cur], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -228,8 +222,8 @@ static int repro_fold(kid_handle *h, bool thermo, bool spread, long long k0, lon
   const unsigned ncell = (unsigned)h->ncell;
   hipLaunchKernelGGL(repro_cell_key_kernel, grid, block, 0, h->stream, (const int32_t *)h->rp.key, (const int *)h->rp.srows, h->rp.k32[0], h->rp.rows[0], n, k0, k0 + klen, ncell);
   const unsigned bits = 32u - (unsigned)__builtin_clz(ncell);   // keys 0 .. ncell
-  size_t bytes = h->rp.tmp_bytes;
-  KID_HIP(h, rocprim::radix_sort_pairs(h->rp.tmp, bytes, h->rp.k32[0], h->rp.k32[1], h->rp.rows[0], h->rp.rows[1], (size_t)n, 0, bits, h->stream));
+  size_t bytes = h->rp.tmp.bytes;
+  KID_HIP(h, rocprim::radix_sort_pairs(h->rp.tmp.p, bytes, h->rp.k32[0], h->rp.k32[1], h->rp.rows[0], h->rp.rows[1], (size_t)n, 0, bits, h->stream));
   hipLaunchKernelGGL(repro_cell_start_kernel, grid, block, 0, h->stream, (const unsigned *)h->rp.k32[1], h->rp.cs, n, ncell);
   // every plane the launch may have written (the row masks say which it did write)
   FoldTab ft{};
@@ -262,15 +256,16 @@ extern "C" int kid_set_reproducible_sums(kid_handle *h, int on) {
   if (!h) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
   if (!on) {
-    if (h->repro) { KID_HIP(h, hipStreamSynchronize(h->stream)); repro_free(h); }
+    if (!h->repro) return KID_OK;
     h->repro = false;
-    return KID_OK;
+    KID_HIP(h, hipStreamSynchronize(h->stream));
+    return repro_free(h);
   }
   h->repro = true;
   int rc = repro_refuse(h);
   if (!rc) rc = lanes_drain(h);   // the slow-lane schedule is not used in this mode
   if (!rc) rc = rebin_flush(h);   // nor is the re-binning instance of the hot build
   if (!rc) rc = repro_alloc(h);
-  if (rc) { repro_free(h); h->repro = false; }
+  if (rc) { (void)repro_free(h); h->repro = false; }
   return rc;
 }

@@ -152,17 +152,12 @@ static int traj_reserve(kid_handle *h, long long want) {   // room for `want` re
   if (want <= h->traj_capacity) return KID_OK;
   long long cap = std::max<long long>(want, std::max<long long>(2 * h->traj_capacity, 1024));
   KID_HIP(h, hipStreamSynchronize(h->stream));
-  auto grow = [&](void **p, size_t elem) -> int {
-    void *q = nullptr;
-    KID_HIP(h, hipMalloc(&q, (size_t)cap * elem));
-    if (*p) { KID_HIP(h, hipMemcpy(q, *p, (size_t)h->traj_capacity * elem, hipMemcpyDeviceToDevice)); (void)hipFree(*p); }
-    *p = q; return KID_OK;
-  };
-  for (int f = 0; f < KID_NTRAJ_VARS; ++f) if (h->traj_nf > f || h->d_traj_f[f]) { const int rc = grow((void **)&h->d_traj_f[f], sizeof(double)); if (rc) return rc; }
-  { int rc = grow((void **)&h->d_traj_day, sizeof(double)); if (rc) return rc; }
-  { int rc = grow((void **)&h->d_traj_id, sizeof(int64_t)); if (rc) return rc; }
-  { int rc = grow((void **)&h->d_traj_year, sizeof(int32_t)); if (rc) return rc; }
-  { int rc = grow((void **)&h->d_traj_nbonds, sizeof(int32_t)); if (rc) return rc; }
+  const size_t keep = (size_t)h->traj_capacity;
+  for (int f = 0; f < KID_NTRAJ_VARS; ++f) if (h->traj_nf > f || h->d_traj_f[f]) KID_HIP(h, h->mem.regrow(h->d_traj_f[f], keep, (size_t)cap));
+  KID_HIP(h, h->mem.regrow(h->d_traj_day, keep, (size_t)cap));
+  KID_HIP(h, h->mem.regrow(h->d_traj_id, keep, (size_t)cap));
+  KID_HIP(h, h->mem.regrow(h->d_traj_year, keep, (size_t)cap));
+  KID_HIP(h, h->mem.regrow(h->d_traj_nbonds, keep, (size_t)cap));
   h->traj_capacity = cap;
   return KID_OK;
 }
@@ -171,14 +166,9 @@ static int btraj_reserve(kid_handle *h, long long want) {   // room for `want` b
   if (want <= h->btraj_capacity) return KID_OK;
   const long long cap = std::max<long long>(want, std::max<long long>(2 * h->btraj_capacity, 1024));
   KID_HIP(h, hipStreamSynchronize(h->stream));
-  auto grow = [&](void **p, size_t elem) -> int {
-    void *q = nullptr;
-    KID_HIP(h, hipMalloc(&q, (size_t)cap * elem));
-    if (*p) { KID_HIP(h, hipMemcpy(q, *p, (size_t)h->btraj_capacity * elem, hipMemcpyDeviceToDevice)); (void)hipFree(*p); }
-    *p = q; return KID_OK;
-  };
-  for (int f = 0; f < BT_NF64; ++f) { const int rc = grow((void **)&h->d_btraj_f[f], sizeof(double)); if (rc) return rc; }
-  for (int f = 0; f < 2; ++f) { int rc = grow((void **)&h->d_btraj_id[f], sizeof(int64_t)); if (rc) return rc; rc = grow((void **)&h->d_btraj_i[f], sizeof(int32_t)); if (rc) return rc; }
+  const size_t keep = (size_t)h->btraj_capacity;
+  for (int f = 0; f < BT_NF64; ++f) KID_HIP(h, h->mem.regrow(h->d_btraj_f[f], keep, (size_t)cap));
+  for (int f = 0; f < 2; ++f) { KID_HIP(h, h->mem.regrow(h->d_btraj_id[f], keep, (size_t)cap)); KID_HIP(h, h->mem.regrow(h->d_btraj_i[f], keep, (size_t)cap)); }
   h->btraj_capacity = cap;
   return KID_OK;
 }
@@ -194,7 +184,7 @@ int kid_record_posn(kid_handle *h) {
   { const int rc = refresh_tables(h); if (rc) return rc; }
   int fields[KID_NTRAJ_VARS];
   h->traj_nf = traj_fields(h, fields);
-  if (!h->d_traj_cursor) { KID_HIP(h, hipMalloc(&h->d_traj_cursor, 4 * sizeof(unsigned long long))); KID_HIP(h, hipMemsetAsync(h->d_traj_cursor, 0, 4 * sizeof(unsigned long long), h->stream)); }
+  if (!h->d_traj_cursor) KID_HIP(h, h->mem.dev(h->d_traj_cursor, 4, 0));
   { const int rc = traj_reserve(h, h->traj_count_bound + h->n); if (rc) return rc; }
   TrajDev td{}; td.nf = h->traj_nf;
   for (int f = 0; f < td.nf; ++f) { td.src[f] = h->bp.f[fields[f]]; td.dst[f] = h->d_traj_f[f]; }

@@ -37,7 +37,7 @@ module kid_hip_mod
   public :: kid_num_traj_records, kid_profile_enable, kid_profile_get, kid_restart_count_bergs
   public :: kid_restart_read_bergs, kid_restart_read_bonds, kid_restart_write_bergs, kid_restart_write_bonds
   public :: kid_set_conglom_ids, kid_set_forcing_device, kid_set_iceberg_counter, kid_set_resort_interval
-  public :: kid_set_reproducible_sums, kid_rebin_fused_count
+  public :: kid_set_reproducible_sums, kid_rebin_fused_count, kid_memory_in_use
   public :: kid_set_side_stream, kid_set_store_environment, kid_set_stream, kid_sizeof, kid_step_prepare
   public :: kid_upload_bonds, kid_version
   public :: kid_initialize_bonds, kid_count_bonds
@@ -371,6 +371,10 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int64_t
       type(c_ptr), value :: h
       integer(c_int64_t), intent(out) :: count
+    end function
+    integer(c_int) function kid_memory_in_use(device_bytes, pinned_bytes) bind(C, name='kid_memory_in_use')
+      import :: c_int, c_int64_t
+      integer(c_int64_t), intent(out) :: device_bytes, pinned_bytes
     end function
     integer(c_int) function kid_upload_bonds(h, soa) bind(C, name='kid_upload_bonds')
       import :: c_int, c_ptr, kid_bond_soa

@@ -13,7 +13,7 @@ SO_PATH = os.environ.get("KID_HIP_SO", os.path.join(_CSRC, "libkid_hip.so"))  # 
 
 # every symbol include/kid.h declares (checked by tests/test_abi.py without a GPU)
 SYMBOLS = [
-    "kid_create", "kid_destroy", "kid_set_params", "kid_set_stream", "kid_sync", "kid_last_error", "kid_version",
+    "kid_create", "kid_destroy", "kid_memory_in_use", "kid_set_params", "kid_set_stream", "kid_sync", "kid_last_error", "kid_version",
     "kid_sizeof", "kid_set_static_grid", "kid_set_forcing", "kid_set_forcing_device", "kid_upload_bergs", "kid_download_bergs",
     "kid_num_bergs", "kid_compact_bergs", "kid_move_berg_between_cells", "kid_set_resort_interval", "kid_zero_accumulators", "kid_interp_gridded_fields_to_bergs",
     "kid_evolve_icebergs", "kid_footloose_calving", "kid_set_footloose_step", "kid_get_footloose_step", "kid_footloose_uniform", "kid_thermodynamics", "kid_create_gridded_icebergs_fields",
@@ -74,6 +74,7 @@ def load():
     lib.kid_sizeof.argtypes = [C.c_int]
     lib.kid_create.argtypes = [C.POINTER(T.GridDesc), C.POINTER(T.Params), C.c_int64, C.c_int, C.POINTER(H)]
     lib.kid_destroy.argtypes = [H]
+    lib.kid_memory_in_use.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.kid_set_params.argtypes = [H, C.POINTER(T.Params)]
     lib.kid_set_stream.argtypes = [H, C.c_void_p]
     lib.kid_sync.argtypes = [H]

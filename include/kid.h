@@ -51,7 +51,13 @@ enum {
 /* ---- lifetime ---- */
 int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capacity, int device,
                kid_handle **out);
+/* Frees everything the handle allocated (buffers the caller bound with kid_bind_* stay the caller's).  If the runtime refuses a
+ * free the rest is freed all the same, KID_EHIP is returned and kid_last_error(NULL), called by the same thread, names the
+ * first failure. */
 int kid_destroy(kid_handle *h);
+/* Bytes of device and of pinned host memory that the live handles of this process hold at the moment, all devices together
+ * (either pointer may be NULL).  A handle's share is back at what it was before kid_create once kid_destroy has returned. */
+int kid_memory_in_use(int64_t *device_bytes, int64_t *pinned_bytes);
 int kid_set_params(kid_handle *h, const kid_params *params);
 /* Launch on an existing hipStream_t (e.g. PyTorch's current stream).  NULL names the device's default (null) stream;
  * a handle that is never given a stream uses a private non-blocking one. */
