@@ -5,11 +5,10 @@
 #include "kid_device.hpp"
 #include "kid_thermo.hpp"
 #include "kid_footloose.hpp"
+#include "kid_launch_select.hpp"   // the phase masks PH_*
 
 namespace {
 using namespace kid;
-
-enum : unsigned { PH_INTERP = 1u, PH_EVOLVE = 2u, PH_THERMO = 4u, PH_SPREAD = 8u, PH_FL = 16u, PH_TSPREAD = 32u };   // PH_FL: footloose_calving between evolve and thermodynamics
 
 struct BergPtrs {
   double *f[KID_NB_F64];

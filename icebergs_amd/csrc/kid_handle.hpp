@@ -76,7 +76,7 @@ struct kid_handle {
   bool env_off_requested = false;          // kid_set_store_environment(h, 0)
   double *d_orient = nullptr;              // bond-derived hexagon orientation per berg (mts / interacting bergs)
   hipEvent_t evF[2] = {nullptr, nullptr}, evG[2] = {nullptr, nullptr}; bool evG_live[2] = {false, false};
-  // "slow lane" schedule (kid_set_side_stream mode 2, launch_berg_lanes)
+  // "slow lane" schedule (kid_set_side_stream mode 2, launch_berg_lanes in kid_launch.inc)
   int side_mode = 0; int *d_lane = nullptr, *d_lane_alt = nullptr; hipEvent_t evR = nullptr; int lane_step = 1; bool lanes_active = false, carry_valid = false, evC_live = false;
   hipEvent_t evC = nullptr, evP = nullptr;
   VelRec *d_vel2 = nullptr; TrcRec *d_trc2 = nullptr; DevGrid *d_grid2 = nullptr; int forc_parity = 0;  // forcing records of the odd steps
@@ -97,7 +97,7 @@ struct kid_handle {
   double *d_perm_spare = nullptr;
   BergPtrs bp_alt{};            // second set of field arrays: the re-binning writes all fields there in one launch, then swaps
   // A re-binning whose permutation is known (rebin_plan) but whose copy has not run (rebin_apply): the next whole-population
-  // plain hot build takes its rows through the permutation itself (launch_berg); anything else that looks at rows, row
+  // plain hot build takes its rows through the permutation itself (launch_phase, kid_launch.inc); anything else that looks at rows, row
   // numbers or the pointer tables runs the copy first (rebin_flush).  Nothing of this state is visible from outside.
   bool rebin_pending = false;
   int64_t rebin_fused_count = 0;   // re-binnings taken by that launch so far (kid_rebin_fused_count: tests, A/B runs)
@@ -164,8 +164,8 @@ static int refresh_tables(kid_handle *h);
 static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one)
 static int rebin_plan(kid_handle *h);
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count), rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);
-static bool plain_namelist(const kid_handle *h), lanes_eligible(const kid_handle *h);
-static int repro_refuse(kid_handle *h), repro_fold(kid_handle *h, bool thermo, bool spread, long long k0, long long klen);                   // kid_repro.inc
-static int mts_depth(kid_handle *h), mts_check_timeout(kid_handle *h), mts_fold_scalars(kid_handle *h), bond_orientations(kid_handle *h);   // kid_mts_host.inc
+static bool plain_namelist(const kid_handle *h), lanes_eligible(const kid_handle *h);   // kid_launch.inc
+static int repro_refuse(kid_handle *h);                                                  // kid_repro.inc
+static int mts_check_timeout(kid_handle *h), mts_fold_scalars(kid_handle *h);            // kid_mts_host.inc
 static int halo_bergs_supported(kid_handle *h, const char *what);                                                                           // kid_halo_bergs.inc
 }

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <unordered_map>
 #include <hip/hip_runtime.h>
@@ -34,8 +35,8 @@ using namespace kid;
 // the plain hot build of the fused RK4 step: its own translation unit in the product build (kid_hot_plain.hip, another machine
 // scheduler), included here in a one-file build
 #ifdef KID_HOT_PLAIN_SEPARATE
-namespace kid { int launch_hot_plain(int K, unsigned nblocks, void *stream, const DevGrid *gtab, const kid_params *pp, const void *bp, long long n, double *acc,
-                                     size_t ncell, const void *flags, const void *redo); }
+namespace kid { void launch_hot_plain(bool store_env, bool rebin, unsigned nblocks, void *stream, const DevGrid *gtab, const kid_params *pp, const void *bp, long long n,
+                                      double *acc, size_t ncell, const void *flags, const void *redo); }
 #else
 #include "kid_hot_plain.inc"
 #endif
@@ -620,7 +621,7 @@ static int join_side(kid_handle *h) {
 }
 // Leave the slow-lane schedule: both lanes are complete through the last step once the side stream is joined, so every
 // berg can go back to the hot build and nothing is carried over.  Needed before anything that moves rows (the lists
-// hold row numbers) or that launches outside launch_berg_lanes.
+// hold row numbers) or that launches outside launch_berg_lanes (kid_launch.inc).
 static int lanes_drain(kid_handle *h) {
   const int rc = join_side(h);
   if (rc || !h->lanes_active) return rc;
@@ -963,9 +964,9 @@ static bool field_never_written(const kid_handle *h, int f) {
 // environment selects a stable comparison sort instead.
 // Correctness never depends on it (the kernels accept any order); speed does: the hot build shares LDS cell
 // packets and atomics between the lanes of a wave that sit in the same cell.
-// Is a step of this handle ONE plain hot build over the whole population (kid_step_local's last branch -> launch_berg with
-// evolve | thermo | spread)?  Only then can the copy of a re-binning wait for the step: asked when the re-binning is planned,
-// at the head of kid_step_local and by launch_berg itself.  The slow-lane schedule (it re-bins inside the step, with the
+// Is a step of this handle ONE plain hot build over the whole population (kid_step_local's default family -> launch_phase with
+// evolve | thermo | spread, kid_launch.inc)?  Only then can the copy of a re-binning wait for the step: asked when the re-binning is planned,
+// at the head of kid_step_local and by launch_phase itself.  The slow-lane schedule (it re-bins inside the step, with the
 // copy), the two-halves schedule and reproducible sums keep the eager copy; so does a decomposed run, which packs its
 // emigrants right after the re-binning.
 static bool rebin_fusable(const kid_handle *h) {
@@ -1121,7 +1122,7 @@ int kid_set_resort_interval(kid_handle *h, int steps) {
 // With .not.old_interp_flds_order the stored environment (berg%uo ... od) is an input of evolve_icebergs and thermodynamics as
 // the reference calls them, one after the other; the fused step (kid_run_step / kid_step_local) interpolates it for itself
 // and only writes it -- 104 B per berg-step that nothing inside the library reads back.  Switching the store off is
-// therefore allowed there too; the entry points that do read it then refuse to run (launch_berg) instead of reading values
+// therefore allowed there too; the entry points that do read it then refuse to run (launch_phase, kid_launch.inc) instead of reading values
 // of some earlier step.
 int kid_set_store_environment(kid_handle *h, int on) {
   if (!h) return KID_EINVAL;
@@ -1142,249 +1143,8 @@ int kid_zero_accumulators(kid_handle *h) {
 
 }  // extern "C"
 
-// May the hot build be the plain one (berg_kernel<..., K = 1>, kid_device.hpp)?  Only when every switch of KID_SWITCHES
-// has the value that build folds in, and none of the handle's flags is set.
-static bool plain_namelist(const kid_handle *h) {
-  const kid_params &p = h->params;
-  bool same = true;
-#define KID_X(name, plain, flp) same = same && (p.name == (decltype(p.name))(plain));
-  KID_SWITCHES(KID_X)
-#undef KID_X
-  const Flags &f = h->flags;
-  return same && h->gd.grid_is_latlon && !p.pass_fields_to_ocean_model && !f.has_static && !f.has_fl && !f.footprint && !f.no_diag &&
-         !h->dbg.no_plain_build;
-}
-// ... and K = 2 with the footloose profile's (Cartesian grid, footloose state, no static bergs, no footprint planes)
-static bool fl_profile_namelist(const kid_handle *h) {
-  const kid_params &p = h->params;
-  bool same = true;
-#define KID_X(name, plain, flp) same = same && (p.name == (decltype(p.name))(flp));
-  KID_SWITCHES(KID_X)
-#undef KID_X
-  const Flags &f = h->flags;
-  return same && !h->gd.grid_is_latlon && !p.pass_fields_to_ocean_model && !f.has_static && f.has_fl && !f.footprint && !f.no_diag && !h->dbg.no_plain_build;
-}
-// the staging instance (reproducible sums): hot and general build of the general switches (K = 0), both on the main stream
-template <bool RKV, bool OLDV, unsigned PH>
-static void launch_stage(kid_handle *h, unsigned nbp, const DevGrid *gtab, const Redo &redo, long long klen) {
-  if constexpr ((PH & (PH_THERMO | PH_SPREAD)) != 0) {
-    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true, 0, true>), dim3(nbp), dim3(KID_HOT_WG), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);
-    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false, 0, true>), dim3((unsigned)std::min<long long>((klen + 63) / 64, 2048)), dim3(64), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);
-  }
-}
-template <unsigned PH>
-static int launch_berg(kid_handle *h, long long range_k0 = 0, long long range_len = -1) {   // range: the rows to step (default all)
-  if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
-  if (h->n == 0 || range_len == 0) return KID_OK;
-  const bool rk = h->params.Runge_not_Verlet != 0, old = h->params.old_interp_flds_order != 0;
-  if (!old && !(PH & PH_INTERP) && (PH & (PH_EVOLVE | PH_THERMO)) && !h->flags.store_env) {
-    h->err = "this entry point reads the bergs' stored environment, which kid_set_store_environment has switched off (use kid_run_step, or switch it on)";
-    return KID_EINVAL;
-  }
-  { const int rc_r = repro_refuse(h); if (rc_r) return rc_r; }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-{ int rc_t = lanes_drain(h); if (rc_t) return rc_t; }
-  // A pending re-binning: the whole-population plain hot build takes its rows through the permutation (the re-binning
-  // instance, kid_berg_kernel.hpp) and the general build that follows finds them in the new arrays; every other launch
-  // gets the rows copied first.
-  RebinTab rtab;
-  bool rebin_fused = false;
-  int rebin_rc = KID_OK;
-  if (h->rebin_pending) {
-    rebin_fused = PH == (PH_EVOLVE | PH_THERMO | PH_SPREAD) && rebin_fusable(h) && range_k0 == 0 && range_len < 0 && h->rplan.n == h->n &&
-                  rebin_table(h, h->flags.store_env ? 3 : 1, rtab);
-    if (!rebin_fused) { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
-  }
-{ int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
-  const DevGrid *gtab = h->forc_parity ? h->d_grid2 : h->d_grid;
-  h->tail_valid = false;
-  if (h->flags.store_env || !old) h->env_ever_stored = true;
-  // pass 1: every berg through the specialised build; pass 2: the general build over the bergs pass 1 queued
-  // (a few per cent: cell crossings, coast bounces, polar cells).  Pass 2 is sized for the worst case and its
-  // surplus workgroups exit on the device-side count.
-  // Pipelined (a side stream is set): two halves; the general build of a half runs on the side stream while the main
-  // stream is already in the hot build of the other half (or of the next step): the ~85 us single-wave latency of the
-  // general build leaves the critical path.  Events order a half's hot build behind its own previous general build.
-  const bool plain = plain_namelist(h);   // the hot build of the default namelist carries none of the other branches
-  const bool flprof = fl_profile_namelist(h);   // ... nor does the one of the footloose profile
-  constexpr bool SCATTER = (PH & (PH_THERMO | PH_SPREAD)) != 0;
-  const bool stage = SCATTER && h->repro;   // the staging instance (kid_repro.inc); one part, no pipelining
-  const int nparts = (h->pipelined && !stage && !h->params.mts && !h->params.footloose && h->n >= 4096 && range_len < 0) ? 2 : 1;
-  const long long half = ((h->n / 2 + 255) / 256) * 256;
-  for (int part = 0; part < nparts; ++part) {
-    const long long k0 = (nparts == 1) ? range_k0 : (part == 0 ? 0 : half);
-    const long long klen = (nparts == 1) ? (range_len < 0 ? h->n : range_len) : (part == 0 ? half : h->n - half);
-    const unsigned nbp = (unsigned)((klen + KID_HOT_WG - 1) / KID_HOT_WG);
-    Redo redo{part == 0 ? h->d_redo_list : h->d_redo_list2, h->d_redo_cnt[part][h->redo_parity], k0, klen, nullptr, 0,
-              h->d_fl_cursor, h->d_iceberg_counter, (long long)h->capacity, h->gd.iec - h->gd.isc + 1, h->fl_step,
-              StageTab{h->rp.stage, h->rp.key, h->rp.mask, (long long)h->capacity}};
-    if (rebin_fused) {
-      hipLaunchKernelGGL(set_rebin_table_kernel, dim3(1), dim3(64), 0, h->stream, rtab, h->d_rb);
-      redo.rb = h->d_rb; redo.perm = h->rplan.perm;
-    }
-    hipStream_t gs = (nparts == 2) ? h->side_stream : h->stream;
-    if (h->evG_live[part]) KID_HIP(h, hipStreamWaitEvent(h->stream, h->evG[part], 0));
-    if (nparts == 1 && h->evG_live[1]) KID_HIP(h, hipStreamWaitEvent(h->stream, h->evG[1], 0));
-    if (!h->redo_prezeroed) KID_HIP(h, hipMemsetAsync(redo.count, 0, sizeof(int), h->stream));
-    if (h->profile) {  // one (start, stop) pair around every hot-build launch
-      KID_HIP(h, hipEventCreate(&e0)); KID_HIP(h, hipEventCreate(&e1));
-      KID_HIP(h, hipEventRecord(e0, h->stream));
-    }
-#define KID_LAUNCH(RKV, OLDV)                                                                                                   \
-  do {                                                                                                                          \
-    if (stage) {  /* (profiling times the hot and the general build together here) */                                        \
-      launch_stage<RKV, OLDV, PH>(h, nbp, gtab, redo, klen);                                                                    \
-      if (h->profile) { (void)hipEventRecord(e1, h->stream); h->pending.emplace_back(e0, e1); h->berg_launches++; }             \
-      h->evG_live[part] = false;                                                                                                \
-      break;                                                                                                                    \
-    }                                                                                                                           \
-    if (PH == (PH_EVOLVE | PH_THERMO | PH_SPREAD) && RKV && OLDV && plain)                                                       \
-      (void)kid::launch_hot_plain((rebin_fused ? -1 : 1) * (h->flags.store_env ? 3 : 1), nbp, (void *)h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &redo);  \
-    else if (PH == (PH_INTERP | PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD) && !RKV && !OLDV && flprof)                           \
-      hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true, (PH == (PH_INTERP | PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD) && !RKV && !OLDV) ? 2 : 0>), dim3(nbp), dim3(KID_HOT_WG), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);  \
-    else                                                                                                                        \
-    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true>), dim3(nbp), dim3(KID_HOT_WG), 0, h->stream, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo);  \
-    if (h->profile) { (void)hipEventRecord(e1, h->stream); h->pending.emplace_back(e0, e1); h->berg_launches++; } /* the timed kernel is the hot build (pass 1) */ \
-    if (rebin_fused) { /* the rows are in the second set of arrays now: the general build reads them there */                  \
-      h->rebin_pending = false; redo.rb = nullptr; redo.perm = nullptr; h->rebin_fused_count++;                                 \
-      rebin_rc = rebin_swap(h);                                                                                                 \
-      if (rebin_rc) break;   /* (the table could not follow the rows: nothing more is launched on them) */                     \
-    }                                                                                                                           \
-    if (nparts == 2) { (void)hipEventRecord(h->evF[part], h->stream); (void)hipStreamWaitEvent(gs, h->evF[part], 0); }          \
-    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false>), dim3((unsigned)std::min<long long>((klen + 63) / 64, 2048)), dim3(64), 0, gs, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, redo); \
-    if (nparts == 2) { (void)hipEventRecord(h->evG[part], gs); h->evG_live[part] = true; } else h->evG_live[part] = false;      \
-  } while (0)
-    if (rk && old) KID_LAUNCH(true, true);
-    else if (rk && !old) KID_LAUNCH(true, false);
-    else if (!rk && old) KID_LAUNCH(false, true);
-    else KID_LAUNCH(false, false);
-#undef KID_LAUNCH
-  }
-  if (nparts == 1) h->evG_live[1] = false;
-  h->redo_prezeroed = false;
-  if (rebin_rc) return rebin_rc;
-  KID_HIP(h, hipGetLastError());
-  if (stage) return repro_fold(h, (PH & PH_THERMO) != 0, (PH & (PH_SPREAD | PH_TSPREAD)) != 0, range_k0, range_len < 0 ? h->n : range_len);
-  return KID_OK;
-}
-
-// The "slow lane" schedule of the fused step (kid_set_side_stream mode 2).  The general build is a single-wave latency
-// (~65 us for the few per cent of bergs that cross a cell edge or bounce) during which the chip idles.  Here it never
-// sits between two hot builds: a berg the hot build of step s hands over is stepped by general-build launches on the
-// side stream for steps s and s + 1 and returns to the hot build at s + 2:
-//   main: prepass(s) | hot(s) ..................................... | prepass(s+1) | hot(s+1) ...
-//   side:            | carry(s): step s of the bergs handed over at s-1 | new(s): step s of those handed over at s | gather(s)
-// carry(s) starts with hot(s) and is long finished when hot(s+1) starts (event evC, normally already signalled);
-// new(s) runs under hot(s+1), which skips its bergs (lane[k] >= s+1).  Per-step sums go to the accumulator block bound
-// at launch; the caller alternates two blocks and launches the gather on the side stream (PipelinedStepper).
-static bool lanes_eligible(const kid_handle *h) {
-  const kid_params &p = h->params;
-  return h->side_mode == 2 && h->side_stream && !h->repro && !p.static_icebergs && !p.mts && !p.interactive_icebergs_on &&
-         !p.footloose && !(p.grounding_fraction > 0.) && !p.find_melt_using_spread_mass && h->n >= 4096;
-}
-template <bool OLDV>
-static int launch_berg_lanes(kid_handle *h) {
-  constexpr unsigned PH = OLDV ? (PH_EVOLVE | PH_THERMO | PH_SPREAD) : (PH_INTERP | PH_EVOLVE | PH_THERMO | PH_SPREAD);
-  if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (this schedule re-bins inside the step, with the copy)
-  { int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
-  const bool rk = h->params.Runge_not_Verlet != 0;
-  const DevGrid *gtab = h->forc_parity ? h->d_grid2 : h->d_grid;
-  hipStream_t M = h->stream, S = h->side_stream;
-  const int s = h->lane_step, par = s & 1;
-  h->tail_valid = false;
-  if (h->flags.store_env || !OLDV) h->env_ever_stored = true;
-  h->lanes_active = true;
-  for (int q = 0; q < 2; ++q) if (h->evG_live[q] && h->pipelined) { KID_HIP(h, hipStreamWaitEvent(M, h->evG[q], 0)); h->evG_live[q] = false; }
-  if (!h->redo_prezeroed) {  // no prepass: zero this step's counter here (it was last read by the previous carry-over launch)
-    if (h->evC_live) KID_HIP(h, hipStreamWaitEvent(M, h->evC, 0));
-    KID_HIP(h, hipMemsetAsync(h->d_redo_cnt[0][par], 0, sizeof(int), M));
-  }
-  int *list_new = par ? h->d_redo_list2 : h->d_redo_list, *list_old = par ? h->d_redo_list : h->d_redo_list2;
-  const Redo hot{list_new, h->d_redo_cnt[0][par], 0, h->n, h->d_lane, s};
-  const Redo carry{list_old, h->d_redo_cnt[0][par ^ 1], 0, h->n, nullptr, 0};
-  const unsigned nbp = (unsigned)((h->n + KID_HOT_WG - 1) / KID_HOT_WG), nbg = (unsigned)std::min<long long>((h->n + 63) / 64, 2048);
-  // Every record / wait is a barrier packet of ~5 us on the stream it goes to: the main stream gets one wait (in the
-  // prepass) and two records per step; with profiling on, the (start, stop) pair of the hot build doubles as the two.
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->profile) { KID_HIP(h, hipEventCreate(&e0)); KID_HIP(h, hipEventCreate(&e1)); }
-  hipEvent_t evP = h->profile ? e0 : h->evP, evF = h->profile ? e1 : h->evF[0];
-  KID_HIP(h, hipEventRecord(evP, M));  // forcing records and accumulator block of this step are ready
-  KID_HIP(h, hipStreamWaitEvent(S, evP, 0));
-#define KID_LAUNCH_LANES(RKV)                                                                                                   \
-  do {                                                                                                                          \
-    if (h->carry_valid)                                                                                                         \
-      hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false>), dim3(nbg), dim3(64), 0, S, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, carry); \
-    /* recorded even without a carry-over launch: everything enqueued on the side stream so far (the gather of the step  \
-       before last included) is complete once the next prepass has waited for it */                                          \
-    (void)hipEventRecord(h->evC, S); h->evC_live = true;                                                                        \
-    if (RKV && OLDV && plain)                                                                                                   \
-      (void)kid::launch_hot_plain(h->flags.store_env ? 3 : 1, nbp, (void *)M, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &hot); \
-    else                                                                                                                        \
-    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, true>), dim3(nbp), dim3(KID_HOT_WG), 0, M, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, hot); \
-    (void)hipEventRecord(evF, M);                                                                                               \
-    if (h->profile) { h->pending.emplace_back(e0, e1); h->berg_launches++; }                                                    \
-    if (rebin_now) {                                                                                                            \
-      /* re-binning inside the step: between the hot build and the general build of the bergs it handed over, whose list  \
-         and lanes move with the rows; nothing is drained and no latency is exposed (the carry-over launch of this step   \
-         is long finished, the main stream only has to say so before it moves rows) */                                      \
-      (void)hipStreamWaitEvent(M, h->evC, 0);                                                                                   \
-      rebin_rc = rebin_core(h, true, list_new, h->d_redo_cnt[0][par]);                                                          \
-      if (!h->evR) (void)hipEventCreateWithFlags(&h->evR, hipEventDisableTiming);                                               \
-      (void)hipEventRecord(h->evR, M); (void)hipStreamWaitEvent(S, h->evR, 0);                                                  \
-    } else (void)hipStreamWaitEvent(S, evF, 0);                                                                                 \
-    hipLaunchKernelGGL((berg_kernel<RKV, OLDV, PH, false>), dim3(nbg), dim3(64), 0, S, gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, h->flags, hot); \
-    (void)hipEventRecord(h->evG[0], S); h->evG_live[0] = true;                                                                  \
-  } while (0)
-  const bool plain = plain_namelist(h);
-  const bool rebin_now = h->resort_interval > 0 && ++h->steps_since_sort >= h->resort_interval && !h->have_bonds && !h->dbg.stable_resort;
-  int rebin_rc = KID_OK;
-  if (rk) KID_LAUNCH_LANES(true); else KID_LAUNCH_LANES(false);
-#undef KID_LAUNCH_LANES
-  if (rebin_rc) return rebin_rc;
-  if (rebin_now) h->steps_since_sort = 0;
-  h->carry_valid = true;
-  h->lane_step = s + 1;
-  h->redo_prezeroed = false;
-  KID_HIP(h, hipGetLastError());
-  return KID_OK;
-}
-
 extern "C" {
 
-int kid_evolve_icebergs_mts(kid_handle *h);
-int kid_evolve_icebergs_interactive(kid_handle *h);
-int kid_interp_gridded_fields_to_bergs(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  { const int rc_h = halo_rows_refuse(h, "kid_interp_gridded_fields_to_bergs"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  int rc = launch_berg<PH_INTERP>(h);
-  if (rc || !h->params.mts) return rc;
-  return mts_depth(h);
-}
-int kid_evolve_icebergs(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  KID_HIP(h, hipSetDevice(h->device));
-  if (h->params.static_icebergs) return KID_OK;  // IB:5428
-  { const int rc_r = repro_refuse(h); if (rc_r) return rc_r; }
-  if (h->params.mts) return kid_evolve_icebergs_mts(h);  // IB:5431
-  if (h->params.interactive_icebergs_on) return kid_evolve_icebergs_interactive(h);
-  return launch_berg<PH_EVOLVE>(h);
-}
-int kid_thermodynamics(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  { const int rc_h = halo_rows_refuse(h, "kid_thermodynamics"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  // find_melt_using_spread_mass: the gridded mass before the melt (grd%spread_mass_old, IB:5490-5503) is gathered inside
-  // kid_step_local only; without it the gather would hand back the bergs' own melt as if the switch were off
-  if (h->params.find_melt_using_spread_mass && (!h->d_spread_mass_old || h->d_spread_mass_old == h->d_spread_mass_old_own)) {
-    h->err = "find_melt_using_spread_mass: the phase entry points do not gather spread_mass_old (IB:5490-5503); use kid_run_step / kid_step_local";
-    return KID_EUNSUPPORTED;
-  }
-  // IB:2872-2873
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_UVEL_ON_OCEAN * h->ncell, 0, 18 * h->ncell * sizeof(double), h->stream));
-  return launch_berg<PH_THERMO>(h);
-}
 static int refresh_tables(kid_handle *h) {
   if (h->tables_dirty) {
     const int rc = join_side(h);  // a general-build launch on the side stream may still be reading the tables
@@ -1503,164 +1263,14 @@ static int launch_gather(kid_handle *h) {
   KID_HIP(h, hipGetLastError());
   return KID_OK;
 }
-int kid_create_gridded_icebergs_fields(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  { const int rc_h = halo_rows_refuse(h, "kid_create_gridded_icebergs_fields"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));  // IB:4984-4987
-  int rc = launch_berg<PH_SPREAD>(h);
-  if (rc) return rc;
-  return launch_gather(h);
-}
-
 #include "kid_mts_host.inc"
 #include "kid_calving.inc"
 #include "kid_repro.inc"
 }  // extern "C"
 #include "kid_bond_init.inc"
 #include "kid_budget.inc"
+#include "kid_launch.inc"
 extern "C" {
-
-int kid_step_local(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  { const int rc_h = halo_rows_refuse(h, "kid_step_local"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  int rc = h->acc_prezeroed ? KID_OK : kid_zero_accumulators(h);  // kid_step_prepare has done it for this step
-  h->acc_prezeroed = false;
-  if (rc) return rc;
-  const kid_params &p = h->params;
-  rc = repro_refuse(h);
-  if (rc) return rc;
-  // a pending re-binning waits for the one launch that can take it (the last branch below); every other kind of step copies first
-  if (h->rebin_pending && !rebin_fusable(h)) {
-    rc = rebin_flush(h);
-    if (rc) return rc;
-  }
-  if (p.mts) {  // IB:5409-5512 with mts=T
-    if (!h->visited) { rc = mts_first_visit(h); if (rc) return rc; }
-    if (!p.static_icebergs) { rc = kid_evolve_icebergs_mts(h); if (rc) return rc; }
-    rc = kid_interp_gridded_fields_to_bergs(h);   // IB:5458
-    if (rc) return rc;
-    rc = kid_set_conglom_ids(h);                  // transfer_mts_bergs, IB:5459
-    if (rc) return rc;
-    rc = bond_orientations(h);
-    if (rc) return rc;
-    return launch_berg<PH_THERMO | PH_SPREAD>(h);
-  }
-  if (p.interactive_icebergs_on) {  // single-time-step scheme with interactions, IB:5409-5512
-    const bool contact = (p.contact_distance > 0.) || (p.contact_spring_coef != p.spring_coef);
-    if (!h->visited) { rc = sts_ia_first_visit(h); if (rc) return rc; }
-    if (!p.old_interp_flds_order) { rc = launch_berg<PH_INTERP>(h); if (rc) return rc; }
-    if (!p.static_icebergs) { rc = kid_evolve_icebergs_interactive(h); if (rc) return rc; }
-    if (contact) { rc = kid_set_conglom_ids(h); if (rc) return rc; }   // IB:5470-5471
-    rc = bond_orientations(h);
-    if (rc) return rc;
-    return p.old_interp_flds_order ? launch_berg<PH_THERMO | PH_SPREAD>(h) : launch_berg<PH_INTERP | PH_THERMO | PH_SPREAD>(h);
-  }
-  if (p.footloose && !p.static_icebergs && !h->dbg.fl_unfused) {
-    // calving sits between evolve and thermodynamics (IB:5453): fused into the per-berg launch (PH_FL), one pass over the
-    // SoA instead of three (320 B per berg-step instead of 530).  The children it appends are new rows; they
-    // owe this step's thermodynamics and spreading, which a second, short launch over those rows delivers.
-    h->flags.has_fl = 1;
-    KID_HIP(h, hipMemsetAsync(h->d_fl_cursor, 0, sizeof(int), h->stream));
-    const long long n_old = h->n;
-    rc = p.old_interp_flds_order ? launch_berg<PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD>(h) : launch_berg<PH_INTERP | PH_EVOLVE | PH_FL | PH_THERMO | PH_SPREAD>(h);
-    const unsigned fl_step_now = h->fl_step;
-    h->fl_step += 1u;   // one footloose pass (hot and general build of this launch share the step word)
-    if (rc) return rc;
-    int appended = 0;  // the population grew: the host needs the new size before the next launch
-    KID_HIP(h, hipMemcpyAsync(&appended, h->d_fl_cursor, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    KID_HIP(h, hipStreamSynchronize(h->stream));
-    if (appended > h->capacity - n_old) {
-      h->n = h->capacity;
-      h->err = "footloose calving ran out of capacity: create the handle with room for child bergs";
-      return KID_ECAPACITY;
-    }
-    h->n = n_old + appended;
-    rc = fl_place_children(h, n_old, appended, fl_step_now);
-    if (rc) return rc;
-    rc = fl_assign_ids(h, n_old, appended);
-    if (rc) return rc;
-    return p.old_interp_flds_order ? launch_berg<PH_THERMO | PH_SPREAD>(h, n_old, appended) : launch_berg<PH_INTERP | PH_THERMO | PH_SPREAD>(h, n_old, appended);
-  }
-  if (p.footloose) {  // phase by phase (KID_FL_UNFUSED, static bergs): three launches
-    // static_icebergs: evolve_icebergs is not called (IB:5428-5436); the calving that follows still is (IB:5453)
-    rc = p.static_icebergs ? launch_berg<PH_INTERP>(h) : launch_berg<PH_INTERP | PH_EVOLVE>(h);
-    if (rc) return rc;
-    rc = kid_footloose_calving(h);
-    if (rc) return rc;
-    return launch_berg<PH_INTERP | PH_THERMO | PH_SPREAD>(h);
-  }
-  if (p.find_melt_using_spread_mass) {
-    // IB:5490-5503: the gridded mass BEFORE the thermodynamics (calculate_mass_on_ocean without diagnostics, the 'mass'
-    // gather into grd%spread_mass_old, planes reset), then thermodynamics + create_gridded_icebergs_fields as usual; the
-    // gather replaces floating_melt by (spread_mass_old - spread_mass)/dt (IB:3436-3445)
-    if (!h->d_spread_mass_old) {
-      KID_HIP(h, h->mem.dev(h->d_spread_mass_old_own, 2 * h->ncell, 0));   // + spread_mass_tmp
-      h->d_spread_mass_old = h->d_spread_mass_old_own;
-    }
-    if (!p.static_icebergs) { rc = p.old_interp_flds_order ? launch_berg<PH_EVOLVE>(h) : launch_berg<PH_INTERP | PH_EVOLVE>(h); if (rc) return rc; }
-    const size_t on_ocean = (size_t)KID_A_MASS_ON_OCEAN * h->ncell, on_bytes = 36 * h->ncell * sizeof(double);
-    KID_HIP(h, hipMemsetAsync(h->d_acc + on_ocean, 0, on_bytes, h->stream));
-    const Flags keep = h->flags;
-    h->flags.no_diag = 1; h->flags.footprint = 0;
-    rc = launch_berg<PH_SPREAD>(h);
-    h->flags = keep;
-    if (rc) return rc;
-    { const int ncomp = (h->gd.iec - h->gd.isc + 1) * (h->gd.jec - h->gd.jsc + 1);
-      hipLaunchKernelGGL(mass_gather_kernel, dim3((unsigned)((ncomp + 255) / 256)), dim3(256), 0, h->stream, dev_grid(h), (const double *)h->d_acc, h->d_spread_mass_old, h->ncell,
-                         h->params.periodic_reentry != 0 && h->gd.Lx > 0.); }
-    KID_HIP(h, hipMemsetAsync(h->d_acc + on_ocean, 0, on_bytes, h->stream));
-    if (p.Iceberg_melt_without_decay) {
-      // the bergs do not decay, so the gridded mass AFTER the melt is what thermodynamics itself spreads (IB:3219-3238);
-      // it is gathered into spread_mass_tmp (IB:3411-3413) before create_gridded_icebergs_fields spreads the unchanged bergs
-      rc = p.old_interp_flds_order ? launch_berg<PH_THERMO | PH_TSPREAD>(h) : launch_berg<PH_INTERP | PH_THERMO | PH_TSPREAD>(h);
-      if (rc) return rc;
-      { const int ncomp = (h->gd.iec - h->gd.isc + 1) * (h->gd.jec - h->gd.jsc + 1);
-        hipLaunchKernelGGL(mass_gather_kernel, dim3((unsigned)((ncomp + 255) / 256)), dim3(256), 0, h->stream, dev_grid(h), (const double *)h->d_acc, h->d_spread_mass_old + h->ncell, h->ncell,
-                           h->params.periodic_reentry != 0 && h->gd.Lx > 0.); }
-      KID_HIP(h, hipMemsetAsync(h->d_acc + on_ocean, 0, on_bytes, h->stream));
-      return launch_berg<PH_SPREAD>(h);
-    }
-    return p.old_interp_flds_order ? launch_berg<PH_THERMO | PH_SPREAD>(h) : launch_berg<PH_INTERP | PH_THERMO | PH_SPREAD>(h);
-  }
-  if (p.old_interp_flds_order) {
-    if (p.static_icebergs) rc = launch_berg<PH_THERMO | PH_SPREAD>(h);
-    else if (lanes_eligible(h)) rc = launch_berg_lanes<true>(h);
-    else rc = launch_berg<PH_EVOLVE | PH_THERMO | PH_SPREAD>(h);
-  } else {
-    // IB:5423: interpolate, evolve; IB:5473: interpolate again at the new position, then thermodynamics.  Per berg that
-    // is one chain, so one launch (the second interpolation sits between the phases inside berg_kernel)
-    if (lanes_eligible(h)) return launch_berg_lanes<false>(h);
-    if (!p.static_icebergs && !h->dbg.new_order_unfused) return launch_berg<PH_INTERP | PH_EVOLVE | PH_THERMO | PH_SPREAD>(h);
-    rc = p.static_icebergs ? launch_berg<PH_INTERP>(h) : launch_berg<PH_INTERP | PH_EVOLVE>(h);
-    if (rc) return rc;
-    rc = launch_berg<PH_INTERP | PH_THERMO | PH_SPREAD>(h);
-  }
-  return rc;
-}
-int kid_step_gather(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  { const int rc_h = halo_rows_refuse(h, "kid_step_gather"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  int rc = launch_gather(h);
-  if (rc) return rc;
-  return KID_OK;
-}
-int kid_run_step(kid_handle *h, int nsteps) {
-  if (!h || nsteps < 0) return KID_EINVAL;
-  for (int s = 0; s < nsteps; ++s) {
-    int rc = kid_step_local(h);
-    if (rc) return rc;
-    rc = kid_step_gather(h);
-    if (rc) return rc;
-    if (!h->lanes_active && !h->params.mts && !h->params.interactive_icebergs_on && h->resort_interval > 0 && ++h->steps_since_sort >= h->resort_interval) {  // IB:5437, amortised; bonded bergs keep their rows
-      rc = kid_move_berg_between_cells(h);
-      if (rc) return rc;
-    }
-  }
-  return KID_OK;
-}
 
 int kid_get_accumulators(kid_handle *h, double *acc, double *out, double *scalars) {
   if (!h) return KID_EINVAL;

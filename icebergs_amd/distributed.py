@@ -135,7 +135,7 @@ class PipelinedStepper:
         # hands over are stepped on the second stream for two steps (kid_set_side_stream mode 2, include/kid.h)
         ib.set_side_stream(self.comm.cuda_stream, 2 if slow_lane else (1 if split_general else 0))
         self.resort_interval, self._since_sort, self.k = resort_interval, 0, 0
-        # Slow lane: the library orders the streams itself (lanes_eligible / launch_berg_lanes in kid_hip.hip): each prepass
+        # Slow lane: the library orders the streams itself (lanes_eligible in csrc/kid_launch_select.hpp, launch_berg_lanes in csrc/kid_launch.inc): each prepass
         # waits for everything enqueued on the second stream up to the previous step's carry-over launch, which follows the
         # gather of the step before; and the second stream waits for the hot build before anything of the step runs on
         # it.  The events below would only add barrier packets (~5 us each) to the critical stream.
@@ -156,7 +156,7 @@ class PipelinedStepper:
 
     @staticmethod
     def _slow_lane_eligible(ib, p):
-        """mirror of lanes_eligible() in csrc/kid_hip.hip: the fused step without footloose, bonds or interactions"""
+        """mirror of lanes_eligible() in csrc/kid_launch_select.hpp: the fused step without footloose, bonds or interactions"""
         return bool(not p.static_icebergs and not p.mts and not p.interactive_icebergs_on
                     and not p.footloose and not (p.grounding_fraction > 0.0) and ib.num_bergs()[0] >= 4096)
 
