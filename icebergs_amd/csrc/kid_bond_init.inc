@@ -202,9 +202,7 @@ extern "C" int kid_initialize_bonds(kid_handle *h, int32_t from_radii, double le
   if (nformed) *nformed = 0;
   if (!h->params.iceberg_bonds_on) { h->err = "kid_initialize_bonds needs iceberg_bonds_on"; return KID_EINVAL; }
   if (h->params.max_bonds > KID_MAX_BONDS || (h->mts_ready && h->mb > KID_MAX_BONDS)) { h->err = "max_bonds out of range"; return KID_EINVAL; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc_e = rows_enter(h, ROWS_CHANGE); if (rc_e) return rc_e; }
   int rc = mts_ensure_default(h);
   if (rc) return rc;
   const long long n = h->n;
@@ -262,9 +260,7 @@ extern "C" int kid_count_bonds(kid_handle *h, int64_t *nbonds, int64_t *unmatche
   if (!h) return KID_EINVAL;
   if (nbonds) *nbonds = 0;
   if (unmatched) *unmatched = 0;
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = join_side(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc_e = rows_enter(h, ROWS_READ); if (rc_e) return rc_e; }
   if (!h->have_bonds || !h->mts_ready || h->n == 0) return KID_OK;
   int rc = mts_refresh(h);
   if (rc) return rc;

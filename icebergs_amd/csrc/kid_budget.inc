@@ -153,9 +153,7 @@ static int budget_ensure(kid_handle *h) {
 }
 
 static int budget_sweep(kid_handle *h, double res[BUD_NRES]) {
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = join_side(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc_e = rows_enter(h, ROWS_READ); if (rc_e) return rc_e; }
   { const int rc = budget_ensure(h); if (rc) return rc; }
   const kid_grid_desc &d = h->gd;
   const kid_params &p = h->params;

@@ -340,9 +340,7 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   if (!h->calving_on) { h->err = "kid_set_calving_params must be called first"; return KID_EINVAL; }
   if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
   if (!h->params.old_interp_flds_order && !h->have_forcing) { h->err = "new bergs interpolate the forcing (IB:6353): set it before kid_calving"; return KID_EINVAL; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc = lanes_drain(h); if (rc) return rc; }   // new rows must start in the hot lane
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }   // new rows must start in the hot lane
   { const int rc = refresh_tables(h); if (rc) return rc; }
   const kid_grid_desc &d = h->gd;
   const size_t n0 = (size_t)(d.iec - d.isc + 1) * (d.jec - d.jsc + 1);
@@ -402,13 +400,5 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   KID_HIP(h, hipStreamSynchronize(h->stream));
   const int appended = (int)(reinterpret_cast<const unsigned long long *>(h->calv_host + KID_NCALV_SCALARS)[0] & 0xffffffffull);
   if (scalars) for (int q = 0; q < KID_NCALV_SCALARS; ++q) scalars[q] = h->calv_host[q];
-  if (appended > 0) { h->tail_valid = false; h->rp.srows_n = -1; if (!h->params.old_interp_flds_order) h->env_ever_stored = true; }
-  const int64_t room = h->capacity - h->n;
-  if (appended > room) {
-    h->n = h->capacity;
-    h->err = "calving ran out of capacity: create the handle with room for new bergs";
-    return KID_ECAPACITY;
-  }
-  h->n += appended;
-  return KID_OK;
+  return rows_appended(h, appended, nullptr, "calving ran out of capacity: create the handle with room for new bergs");
 }

@@ -19,9 +19,7 @@ static inline uint64_t chk_bits(double x) { uint64_t u; std::memcpy(&u, &x, size
 extern "C" int kid_bergs_chksum(kid_handle *h, int64_t out[6]) {
   if (!h || !out) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_bergs_chksum"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = join_side(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc_e = rows_enter(h, ROWS_READ); if (rc_e) return rc_e; }
   const size_t n = (size_t)h->n;
   static const int F[] = {KID_B_LON, KID_B_LAT, KID_B_UVEL, KID_B_VVEL, KID_B_MASS, KID_B_THICKNESS, KID_B_WIDTH, KID_B_LENGTH, KID_B_AXN, KID_B_AYN,
                           KID_B_BXN, KID_B_BYN, KID_B_UVEL_OLD, KID_B_VVEL_OLD, KID_B_LON_OLD, KID_B_LAT_OLD, KID_B_START_DAY, KID_B_START_LON,

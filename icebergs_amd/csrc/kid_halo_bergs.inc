@@ -26,15 +26,8 @@ __device__ __forceinline__ int halo_berg_selected(const HaloBergSel &s, const Be
 }
 // one direction: a reservation per wave (all selected rows are counted), then the first `cap` of them are written
 __device__ __forceinline__ void halo_berg_emit(bool mine, unsigned long long *cursor, double *buf, long long cap, const BergPtrs &b, long long k) {
-  const unsigned long long m = __ballot(mine);
-  if (!m) return;
-  const int lane = (int)__lane_id();
-  unsigned long long base = 0;
-  if (lane == 0) base = atomicAdd(cursor, (unsigned long long)__popcll(m));
-  base = __shfl(base, 0);
-  if (!mine) return;
-  const long long slot = (long long)base + __popcll(m & ((1ull << lane) - 1ull));
-  if (slot < cap) mig_write_record(buf + (size_t)slot * MIG_WIDTH, b, k, 1.);   // FW:1904
+  const long long slot = wave_reserve(mine, cursor);
+  if (slot >= 0 && slot < cap) mig_write_record(buf + (size_t)slot * MIG_WIDTH, b, k, 1.);   // FW:1904
 }
 }  // namespace
 
@@ -45,12 +38,6 @@ __global__ void __launch_bounds__(256) halo_berg_pack_kernel(const BergPtrs b, c
   const int sel = k < n ? halo_berg_selected(s, b, k) : 0;
   halo_berg_emit((sel & 1) != 0, cursor, out.buf[0], out.cap[0], b, k);
   halo_berg_emit((sel & 2) != 0, cursor + 1, out.buf[1], out.cap[1], b, k);
-}
-// resident halo rows
-__global__ void __launch_bounds__(256) halo_berg_count_kernel(const int32_t *alive, const double *halo, long long n, unsigned long long *count) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  const unsigned long long m = __ballot(k < n && alive[k] != 0 && halo[k] >= 0.5);
-  if (m && __lane_id() == 0) atomicAdd(count, (unsigned long long)__popcll(m));
 }
 
 extern "C" {
@@ -90,60 +77,21 @@ int kid_pack_halo_bergs_pair(kid_handle *h, int32_t axis, int32_t width, double 
   }
   h->mig_mode = true;   // a decomposed run, as with the migration calls
   if (!buf_hi && !buf_lo) return KID_OK;   // no neighbour on either side
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc = lanes_drain(h); if (rc) return rc; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }
   if (h->n == 0) return KID_OK;
   const HaloBergSel s{axis, w, buf_hi ? 1 : 0, buf_lo ? 1 : 0, d.isc, d.iec, d.jsc, d.jec, d.isd, d.ied};
   const unsigned nb = (unsigned)((h->n + 255) / 256);
-  // staging as in kid_pack_emigrants: sized from what the previous calls carried; a pass that finds more than fit counts them
-  // all and is repeated once with room for the count
-  long long sc[2] = {0, 0};
-  for (int q = 0; q < 2; ++q) sc[q] = std::min<long long>((long long)capacity[q], std::max<long long>(4096, 2 * h->halo_last[q]));
-  MigOut out{};
-  bool fits = true, any = false;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    { const int rc = mig_stage(h, sc[0] + sc[1]); if (rc) return rc; }
-    out = MigOut{{h->d_mig_buf, h->d_mig_buf + (size_t)sc[0] * MIG_WIDTH}, {sc[0], sc[1]}};
-    KID_HIP(h, hipMemsetAsync(h->d_count, 0, 2 * sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(halo_berg_pack_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp, s, (long long)h->n, h->d_count, out);
-    KID_HIP(h, hipGetLastError());
-    KID_HIP(h, hipMemcpyAsync(mig_pinned_word(h), h->d_count, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    KID_HIP(h, hipStreamSynchronize(h->stream));
-    fits = true; any = false;
-    bool staged = true;
-    for (int q = 0; q < 2; ++q) {
-      const long long c = (long long)mig_pinned_word(h)[q];
-      if (n[q]) *n[q] = c;
-      h->halo_last[q] = c;
-      fits = fits && c <= capacity[q]; any = any || c > 0; staged = staged && c <= sc[q];
-      sc[q] = std::min<long long>((long long)capacity[q], std::max<long long>(sc[q], c));
-    }
-    if (!any || !fits || staged) break;
-  }
-  if (!any) return KID_OK;
-  if (!fits) { h->err = "kid_pack_halo_bergs_pair: a buffer is too small (*n holds the bergs of the strip); nothing was packed"; return KID_ECAPACITY; }
-  for (int q = 0; q < 2; ++q) if (n[q] && *n[q] > 0) std::memcpy(buf[q], out.buf[q], (size_t)*n[q] * MIG_WIDTH * sizeof(double));
-  return KID_OK;
+  bool packed = false;
+  return pack_staged(h, 2, buf, capacity, n, h->halo_last, "kid_pack_halo_bergs_pair: a buffer is too small (*n holds the bergs of the strip); nothing was packed",
+                     [&](const MigOut &out) { hipLaunchKernelGGL(halo_berg_pack_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp, s, (long long)h->n, h->d_count, out); }, packed);
 }
 
 int kid_halo_berg_count(kid_handle *h, int64_t *n) {
   if (!h || !n) return KID_EINVAL;
   *n = 0;
   if (!h->flags.has_static) return KID_OK;   // no row has ever held halo_berg != 0
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = join_side(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
-  if (h->n == 0) return KID_OK;
-  unsigned long long cnt = 0;
-  KID_HIP(h, hipMemsetAsync(h->d_count, 0, sizeof(cnt), h->stream));
-  hipLaunchKernelGGL(halo_berg_count_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->bp.i[KID_BI_ALIVE],
-                     (const double *)h->bp.f[KID_B_HALO_BERG], (long long)h->n, h->d_count);
-  KID_HIP(h, hipGetLastError());
-  KID_HIP(h, hipMemcpyAsync(&cnt, h->d_count, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-  KID_HIP(h, hipStreamSynchronize(h->stream));
-  *n = (int64_t)cnt;
-  return KID_OK;
+  { const int rc = rows_enter(h, ROWS_READ); if (rc) return rc; }
+  return count_rows(h, h->bp.i[KID_BI_ALIVE], h->bp.f[KID_B_HALO_BERG], n);
 }
 
 }  // extern "C"

@@ -32,6 +32,12 @@ struct HipMem : kid::MemOwner<HipAllocator> {
   }
 };
 
+// argument table of permute_all_kernel (kid_rows.inc): entries [0, n8) are 8-byte fields, [n8, n8 + n4) 4-byte
+namespace {
+enum { KID_PERM_MAX = KID_NB_F64 + KID_NB_I32 + 2 };   // every field, the ids, the lane array of the slow-lane schedule
+struct PermTable { const void *src[KID_PERM_MAX]; void *dst[KID_PERM_MAX]; int n8, n4; };
+}  // namespace
+
 struct kid_handle {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -56,9 +62,9 @@ struct kid_handle {
   kid_params *d_params = nullptr; // device copy of the parameter block
   DevGrid *d_grid = nullptr;      // device copy of the grid descriptor (berg_kernel reads it as a table)
   bool tables_dirty = true;
-  double *d_spare_f64 = nullptr; unsigned *d_pos = nullptr, *d_flag = nullptr; Scratch scan_tmp;
+  Scratch scan_tmp;             // the scan of the row flags (kid_compact_bergs)
   unsigned long long *d_count = nullptr;
-  int *d_redo_list = nullptr, *d_redo_count = nullptr;  // bergs the FAST build hands to the general build
+  int *d_redo_list = nullptr;  // bergs the FAST build hands to the general build
   // pipelined launches (kid_set_side_stream): the population goes through the hot build in two halves on the main
   // stream while the general build of each half runs on the side stream, under the hot build of the other half
   hipStream_t side_stream = nullptr; bool pipelined = false;
@@ -94,8 +100,7 @@ struct kid_handle {
   int32_t *d_fl_head = nullptr, *d_fl_next = nullptr; int64_t *d_fl_newid = nullptr; long long fl_ev_capacity = 0;   // fl_assign_ids_*
   unsigned *d_key[2] = {nullptr, nullptr}, *d_idx[2] = {nullptr, nullptr};  // radix-sort ping-pong buffers
   Scratch sort_tmp;
-  double *d_perm_spare = nullptr;
-  BergPtrs bp_alt{};            // second set of field arrays: the re-binning writes all fields there in one launch, then swaps
+  BergPtrs bp_alt{};            // second set of field arrays: a re-binning or compaction writes all fields there in one launch, then swaps (perm_storage)
   // A re-binning whose permutation is known (rebin_plan) but whose copy has not run (rebin_apply): the next whole-population
   // plain hot build takes its rows through the permutation itself (launch_phase, kid_launch.inc); anything else that looks at rows, row
   // numbers or the pointer tables runs the copy first (rebin_flush).  Nothing of this state is visible from outside.
@@ -162,7 +167,7 @@ struct kid_handle {
 extern "C" {
 static int refresh_tables(kid_handle *h);
 static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one)
-static int rebin_plan(kid_handle *h);
+static int rebin_plan(kid_handle *h, bool dead_last);
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count), rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);
 static bool plain_namelist(const kid_handle *h), lanes_eligible(const kid_handle *h);   // kid_launch.inc
 static int repro_refuse(kid_handle *h);                                                  // kid_repro.inc

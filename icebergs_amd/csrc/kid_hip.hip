@@ -20,6 +20,7 @@
 #include <string.h>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include <unordered_map>
 #include <hip/hip_runtime.h>
@@ -29,6 +30,7 @@
 #include "kid_thermo.hpp"
 #include "kid_footloose.hpp"
 #include "kid_berg_kernel.hpp"
+#include "kid_rows_plan.hpp"
 
 using namespace kid;
 
@@ -267,116 +269,6 @@ __global__ void __launch_bounds__(256) mass_gather_kernel(const DevGrid g, const
   plane[c] = dmda;
 }
 
-__global__ void __launch_bounds__(256) count_alive_kernel(const int32_t *alive, long long n, unsigned long long *out) {
-  __shared__ unsigned wsum[4];
-  unsigned local = 0;
-  for (long long k = (long long)blockIdx.x * 256ll + threadIdx.x; k < n; k += (long long)gridDim.x * 256ll) local += alive[k] ? 1u : 0u;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) local += __shfl_xor(local, d);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3]));
-}
-__global__ void __launch_bounds__(256) compact_f64_kernel(const double *src, double *dst, const int32_t *alive, const unsigned *pos, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n && alive[k]) dst[pos[k]] = src[k];
-}
-__global__ void __launch_bounds__(256) compact_i32_kernel(const int32_t *src, int32_t *dst, const int32_t *alive, const unsigned *pos, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n && alive[k]) dst[pos[k]] = src[k];
-}
-__global__ void __launch_bounds__(256) compact_i64_kernel(const int64_t *src, int64_t *dst, const int32_t *alive, const unsigned *pos, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n && alive[k]) dst[pos[k]] = src[k];
-}
-// Rows that must survive a dead-tail drop, a compaction or a re-binning.  In a domain-decomposed run (kid_migrate.inc) a berg
-// that left the tile is a DEAD row whose cell lies outside the computational domain until kid_pack_emigrants has collected
-// it (evolve -> move_berg_between_cells -> send_bergs_to_other_pes is the reference's own order, IB:5433-5447); it counts as
-// occupied here, keeps its cell as sort key and is never stepped (alive = 0).  Once packed, its cell is moved inside.
-struct KeepSel { int isc, iec, jsc, jec; const double *halo; };
-__global__ void __launch_bounds__(256) keep_flags_kernel(const int32_t *alive, const int32_t *ine, const int32_t *jne, const KeepSel s, int32_t *keep, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k >= n) return;
-  const int i = ine[k], j = jne[k];
-  const bool waiting = (i < s.isc || i > s.iec || j < s.jsc || j > s.jec) && !(s.halo && s.halo[k] >= 0.5);   // the selection of FW:3027-3035, 3101-3109
-  keep[k] = (alive[k] != 0 || waiting) ? 1 : 0;
-}
-__global__ void __launch_bounds__(256) alive_to_u32_kernel(const int32_t *alive, unsigned *flag, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n) flag[k] = alive[k] ? 1u : 0u;
-}
-// cell key of every berg (dead bergs sort to the end) + identity permutation, for kid_move_berg_between_cells
-__global__ void __launch_bounds__(256) cell_key_kernel(const int32_t *ine, const int32_t *jne, const int32_t *alive, int isd, int jsd, int ni,
-                                                       unsigned dead_key, unsigned *key, unsigned *idx, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n) {
-    key[k] = alive[k] ? (unsigned)((ine[k] - isd) + (jne[k] - jsd) * ni) : dead_key;
-    idx[k] = (unsigned)k;
-  }
-}
-// Counting sort by cell for kid_move_berg_between_cells: (1) key + rank of every berg within its cell (one atomic per
-// berg on the cell's counter), (2) exclusive scan of the counters, (3) destination row = cell start + rank.  Three small
-// launches instead of the ~20 of a comparison sort of 1e6 pairs; the order of the bergs inside a cell is the order the
-// atomics arrive in (results never depend on the row order, see kid.h).
-__global__ void __launch_bounds__(256) cell_rank_kernel(const int32_t *ine, const int32_t *jne, const int32_t *alive, int isd, int jsd, int ni,
-                                                        unsigned dead_key, unsigned *key, unsigned *rank, unsigned *hist, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  const bool in = k < n;
-  const unsigned c = in ? (alive[k] ? (unsigned)((ine[k] - isd) + (jne[k] - jsd) * ni) : dead_key) : 0xffffffffu;
-  // the SoA is almost sorted: the lanes of a wave form a few runs of equal cell.  One atomic per run (its head lane
-  // adds the run length), not one per berg: ~14 lanes would otherwise queue on the same address.
-  const int lane = (int)__lane_id();
-  const unsigned prev = __shfl_up(c, 1);
-  const bool head = (lane == 0) || (prev != c);
-  const unsigned long long heads = __ballot(head);
-  const unsigned long long below = heads & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull));   // heads at or below this lane
-  const int head_lane = 63 - __clzll(below);
-  const unsigned long long above = (lane == 63) ? 0ull : (heads >> (lane + 1));                  // heads after this lane
-  const int next_head = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
-  unsigned base = 0u;
-  if (head && in) base = atomicAdd(hist + c, (unsigned)(next_head - lane));
-  base = __shfl(base, head_lane);
-  if (in) { key[k] = c; rank[k] = base + (unsigned)(lane - head_lane); }
-}
-__global__ void __launch_bounds__(256) cell_place_kernel(const unsigned *key, const unsigned *rank, const unsigned *start, unsigned *perm, unsigned *inv, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n) { const unsigned pos = start[key[k]] + rank[k]; perm[pos] = (unsigned)k; inv[k] = pos; }
-}
-// a list of row numbers through the re-binning (slow-lane schedule: the bergs handed over by the hot build just before it)
-__global__ void __launch_bounds__(256) translate_list_kernel(int *list, const int *count, const unsigned *inv) {
-  const int total = *count;
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < total; t += gridDim.x * 256) list[t] = (int)inv[list[t]];
-}
-// the canonical order of reproducible sums (kid_repro.inc) through the re-binning: it orders bergs, so only its row numbers change
-__global__ void __launch_bounds__(256) translate_rows_kernel(int *rows, const unsigned *inv, long long n) {
-  const long long q = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (q < n) rows[q] = (int)inv[rows[q]];
-}
-// every field of the SoA through the permutation in ONE launch: a thread owns a destination row, reads the source row
-// number once and walks the fields (the loads of consecutive fields are independent)
-enum { KID_PERM_MAX = KID_NB_F64 + KID_NB_I32 + 2 };   // every field, the ids, the lane array of the slow-lane schedule
-struct PermTable { const void *src[KID_PERM_MAX]; void *dst[KID_PERM_MAX]; int n8, n4; };  // entries [0, n8) are 8-byte fields, [n8, n8 + n4) 4-byte
-__global__ void __launch_bounds__(256) permute_all_kernel(const PermTable t, const unsigned *perm, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k >= n) return;
-  const unsigned p = perm[k];
-  int f = 0;
-  for (; f + 4 <= t.n8; f += 4) {
-    const double a = ((const double *)t.src[f])[p], b = ((const double *)t.src[f + 1])[p], c = ((const double *)t.src[f + 2])[p], d = ((const double *)t.src[f + 3])[p];
-    ((double *)t.dst[f])[k] = a; ((double *)t.dst[f + 1])[k] = b; ((double *)t.dst[f + 2])[k] = c; ((double *)t.dst[f + 3])[k] = d;
-  }
-  for (; f < t.n8; ++f) ((double *)t.dst[f])[k] = ((const double *)t.src[f])[p];
-  for (; f < t.n8 + t.n4; ++f) ((int32_t *)t.dst[f])[k] = ((const int32_t *)t.src[f])[p];
-}
-template <typename TT>
-__global__ void __launch_bounds__(256) permute_kernel(const TT *src, TT *dst, const unsigned *perm, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n) dst[k] = src[perm[k]];
-}
-__global__ void __launch_bounds__(256) fill_i32_kernel(int32_t *p, int32_t v, long long n) {
-  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
-  if (k < n) p[k] = v;
-}
 
 }  // namespace
 
@@ -551,7 +443,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   KID_HIP(h, h->mem.dev(h->d_lane, cap, 0));
   KID_HIP(h, h->mem.dev(h->d_count, 4));
   KID_HIP(h, h->mem.dev(h->d_iceberg_counter, h->ncell, 0));
-  for (int **q : {&h->d_fl_cursor, &h->d_redo_count}) KID_HIP(h, h->mem.dev(*q, 1));
+  KID_HIP(h, h->mem.dev(h->d_fl_cursor, 1));
   for (int **q : {&h->d_redo_list, &h->d_redo_list2}) KID_HIP(h, h->mem.dev(*q, cap));
   KID_HIP(h, h->mem.dev(h->d_redo_count2, 4, 0));
   for (int part = 0; part < 2; ++part) for (int par = 0; par < 2; ++par) h->d_redo_cnt[part][par] = h->d_redo_count2 + (2 * part + par);
@@ -764,16 +656,15 @@ int kid_step_prepare(kid_handle *h, const double *const fields[KID_NFORCING]) {
 }
 
 #include "kid_ingest.inc"
+}  // extern "C"
+#include "kid_rows.inc"
+extern "C" {
 
 int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
   if (!h || !host || host->n < 0) return KID_EINVAL;
   if (host->n > h->capacity) { h->err = "more bergs than capacity"; return KID_ECAPACITY; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
-  h->static_rows_n = -1; h->rp.srows_n = -1;   // the cached order by the static `inorder` keys belongs to the previous population
+  { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }
   const size_t n = (size_t)host->n;
-  bool any_static = false, any_fl = false;
   for (int f = 0; f < KID_NB_F64; ++f) {
     if (host->f64[f]) KID_HIP(h, hipMemcpyAsync(h->bp.f[f], host->f64[f], n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     else KID_HIP(h, hipMemsetAsync(h->bp.f[f], 0, n * sizeof(double), h->stream));
@@ -794,25 +685,9 @@ int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
       }
     }
   } else if (n > 0) { h->err = "ine/jne are required"; return KID_EINVAL; }
-  // which optional per-berg fields can matter at all (avoids streaming all-zero arrays through the kernel)
-  for (size_t k = 0; k < n; ++k) {
-    if (host->f64[KID_B_STATIC_BERG] && host->f64[KID_B_STATIC_BERG][k] != 0.) any_static = true;
-    if (host->f64[KID_B_HALO_BERG] && host->f64[KID_B_HALO_BERG][k] != 0.) any_static = true;
-    if (host->f64[KID_B_MASS_OF_FL_BITS] && host->f64[KID_B_MASS_OF_FL_BITS][k] != 0.) any_fl = true;
-    if (host->f64[KID_B_MASS_OF_FL_BERGY_BITS] && host->f64[KID_B_MASS_OF_FL_BERGY_BITS][k] != 0.) any_fl = true;
-    if (host->f64[KID_B_FL_K] && host->f64[KID_B_FL_K][k] != 0.) any_fl = true;
-  }
-  h->flags.has_static = any_static ? 1 : 0;
-  h->flags.has_fl = (any_fl || h->params.footloose) ? 1 : 0;
-  for (int f = 0; f < KID_NB_F64; ++f) {
-    bool nz = false;
-    if (host->f64[f]) for (size_t k = 0; k < n && !nz; ++k) nz = host->f64[f][k] != 0.;
-    h->uploaded_nonzero[f] = nz;
-  }
-  h->tail_valid = false; h->env_ever_stored = false;
   if (h->bp.orient) { h->bp.orient = nullptr; h->tables_dirty = true; }
-  h->n = host->n;
-  h->visited = false; h->have_bonds = false; h->halo_rows_live = false;
+  rows_replaced(h, host);
+  h->visited = false; h->have_bonds = false;
   KID_HIP(h, hipStreamSynchronize(h->stream));
   return KID_OK;
 }
@@ -820,9 +695,7 @@ int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
 int kid_download_bergs(kid_handle *h, kid_berg_soa *host) {
   if (!h || !host) return KID_EINVAL;
   if (host->n < h->n) { h->err = "host SoA too small"; return KID_EINVAL; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = join_side(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc = rows_enter(h, ROWS_READ); if (rc) return rc; }
   const size_t n = (size_t)h->n;
   for (int f = 0; f < KID_NB_F64; ++f)
     if (host->f64[f]) KID_HIP(h, hipMemcpyAsync(host->f64[f], h->bp.f[f], n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -834,290 +707,6 @@ int kid_download_bergs(kid_handle *h, kid_berg_soa *host) {
   return KID_OK;
 }
 
-// which rows are occupied, for tail drops, compaction and re-binning: `alive`, plus (decomposed runs) the rows still waiting
-// to be packed for a neighbour
-static int layout_flags(kid_handle *h, const int32_t **flags) {
-  *flags = h->bp.i[KID_BI_ALIVE];
-  if (!h->mig_mode || h->n == 0) return KID_OK;
-  if (!h->d_keep) KID_HIP(h, h->mem.dev(h->d_keep, (size_t)h->capacity));
-  const KeepSel ks{h->gd.isc, h->gd.iec, h->gd.jsc, h->gd.jec, h->flags.has_static ? h->bp.f[KID_B_HALO_BERG] : nullptr};
-  hipLaunchKernelGGL(keep_flags_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->bp.i[KID_BI_ALIVE], h->bp.i[KID_BI_INE], h->bp.i[KID_BI_JNE], ks, h->d_keep, (long long)h->n);
-  KID_HIP(h, hipGetLastError());
-  *flags = h->d_keep;
-  return KID_OK;
-}
-
-int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive) {
-  if (!h) return KID_EINVAL;
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = join_side(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
-  if (n_slots) *n_slots = h->n;
-  if (n_alive) {
-    unsigned long long cnt = 0;
-    KID_HIP(h, hipMemsetAsync(h->d_count, 0, sizeof(cnt), h->stream));
-    if (h->n > 0) hipLaunchKernelGGL(count_alive_kernel, dim3((unsigned)std::min<long long>((h->n + 255) / 256, 1024)), dim3(256), 0, h->stream, h->bp.i[KID_BI_ALIVE], (long long)h->n, h->d_count);
-    KID_HIP(h, hipMemcpyAsync(&cnt, h->d_count, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-    KID_HIP(h, hipStreamSynchronize(h->stream));
-    *n_alive = (int64_t)cnt;
-    if (h->tail_valid && h->mig_mode && (int64_t)cnt < h->n) {   // decomposed run: the tail is what is neither alive nor waiting to be packed
-      const int32_t *flags = nullptr;
-      { const int rc = layout_flags(h, &flags); if (rc) return rc; }
-      KID_HIP(h, hipMemsetAsync(h->d_count, 0, sizeof(cnt), h->stream));
-      hipLaunchKernelGGL(count_alive_kernel, dim3((unsigned)std::min<long long>((h->n + 255) / 256, 1024)), dim3(256), 0, h->stream, flags, (long long)h->n, h->d_count);
-      KID_HIP(h, hipMemcpyAsync(&cnt, h->d_count, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-      KID_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (h->tail_valid && (int64_t)cnt < h->n) {  // a re-binning left the dead at the tail: drop them now that the count is known
-      h->n = (int64_t)cnt;
-      h->rp.srows_n = -1;
-      if (n_slots) *n_slots = h->n;
-    }
-  }
-  return KID_OK;
-}
-
-int kid_compact_bergs(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
-  if (h->n == 0) return KID_OK;
-  h->static_rows_n = -1; h->rp.srows_n = -1;   // rows move: the cached traversal orders (mts_build_order, repro_static_order) are of the old rows
-  const long long n = h->n;
-  const unsigned nb = (unsigned)((n + 255) / 256);
-  if (!h->d_spare_f64) {
-    KID_HIP(h, h->mem.dev(h->d_spare_f64, (size_t)h->capacity));
-    for (unsigned **q : {&h->d_pos, &h->d_flag}) KID_HIP(h, h->mem.dev(*q, (size_t)h->capacity));
-    size_t tmp = 0;
-    KID_HIP(h, rocprim::exclusive_scan(nullptr, tmp, h->d_flag, h->d_pos, 0u, (size_t)h->capacity, rocprim::plus<unsigned>(), h->stream));
-    KID_HIP(h, h->mem.reserve(h->scan_tmp, tmp));
-  }
-  const int32_t *live = nullptr;   // alive, or alive + waiting to be packed (decomposed runs)
-  { const int rc_l = layout_flags(h, &live); if (rc_l) return rc_l; }
-  hipLaunchKernelGGL(alive_to_u32_kernel, dim3(nb), dim3(256), 0, h->stream, live, h->d_flag, n);
-  size_t tmp = h->scan_tmp.bytes;
-  KID_HIP(h, rocprim::exclusive_scan(h->scan_tmp.p, tmp, h->d_flag, h->d_pos, 0u, (size_t)n, rocprim::plus<unsigned>(), h->stream));
-  int64_t n_alive = 0;
-  // (the count of rows that stay)
-  {
-    unsigned long long cnt = 0;
-    KID_HIP(h, hipMemsetAsync(h->d_count, 0, sizeof(cnt), h->stream));
-    hipLaunchKernelGGL(count_alive_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024)), dim3(256), 0, h->stream, live, n, h->d_count);
-    KID_HIP(h, hipMemcpyAsync(&cnt, h->d_count, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
-    KID_HIP(h, hipStreamSynchronize(h->stream));
-    n_alive = (int64_t)cnt;   // rows that stay
-  }
-  for (int f = 0; f < KID_NB_F64; ++f) {
-    hipLaunchKernelGGL(compact_f64_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.f[f], h->d_spare_f64, live, h->d_pos, n);
-    std::swap(h->bp.f[f], h->d_spare_f64);
-  }
-  {
-    int64_t *spare = (int64_t *)h->d_spare_f64;  // same element size
-    hipLaunchKernelGGL(compact_i64_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.id, spare, live, h->d_pos, n);
-    double *old = (double *)h->bp.id; h->bp.id = spare; h->d_spare_f64 = old;
-  }
-  const bool keeps_dead = (live != h->bp.i[KID_BI_ALIVE]);   // rows waiting to be packed stay dead: their flag moves with them
-  for (int f = 0; f < KID_NB_I32; ++f) {
-    if (f == KID_BI_ALIVE && !keeps_dead) continue;
-    int32_t *spare = (int32_t *)h->d_flag;  // reuse the flag buffer as int32 spare
-    hipLaunchKernelGGL(compact_i32_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.i[f], spare, live, h->d_pos, n);
-    unsigned *old = (unsigned *)h->bp.i[f]; h->bp.i[f] = spare; h->d_flag = old;
-  }
-  if (!keeps_dead && n_alive > 0) hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)((n_alive + 255) / 256)), dim3(256), 0, h->stream, h->bp.i[KID_BI_ALIVE], 1, (long long)n_alive);
-  KID_HIP(h, hipGetLastError());
-  KID_HIP(h, hipStreamSynchronize(h->stream));
-  h->n = n_alive;
-  h->tables_dirty = true;
-  return KID_OK;
-}
-
-// Fields no kernel of the current configuration ever stores to: if such a field was uploaded as zeros it is zeros
-// forever and a re-binning need not move it (config 2: 32 of the 52 fp64 fields).  Conservative: anything that can
-// append bergs (footloose) or the MTS path writes everything.
-static bool field_never_written(const kid_handle *h, int f) {
-  const kid_params &p = h->params;
-  if (p.footloose || p.mts || h->calving_on) return false;
-  switch (f) {
-    case KID_B_AXN_FAST: case KID_B_AYN_FAST: case KID_B_BXN_FAST: case KID_B_BYN_FAST: case KID_B_ANG_VEL: case KID_B_ANG_ACCEL: case KID_B_ROT:
-    case KID_B_UVEL_OLD: case KID_B_VVEL_OLD: case KID_B_LON_OLD: case KID_B_LAT_OLD:
-      return p.periodic_reentry == 0;   // a berg that re-enters across the seam gets them reset (FW:3573-3577)
-    case KID_B_HALO_BERG: case KID_B_STATIC_BERG: case KID_B_START_LON: case KID_B_START_LAT: case KID_B_START_MASS: case KID_B_HEAT_DENSITY:
-      return true;
-    case KID_B_UVEL_PREV: case KID_B_VVEL_PREV:
-      return p.Runge_not_Verlet != 0;
-    case KID_B_MASS_OF_FL_BITS: case KID_B_MASS_OF_FL_BERGY_BITS: case KID_B_FL_K: case KID_B_START_DAY: case KID_B_MASS_SCALING:
-      return h->flags.has_fl == 0;
-    case KID_B_UO: case KID_B_VO: case KID_B_UI: case KID_B_VI: case KID_B_UA: case KID_B_VA: case KID_B_SSH_X: case KID_B_SSH_Y:
-    case KID_B_SST: case KID_B_SSS: case KID_B_CN: case KID_B_HI: case KID_B_OD:
-      return !h->env_ever_stored;
-    default:
-      return false;
-  }
-}
-
-// move_berg_between_cells (IB:5437, FW:1758-1797): re-bin the bergs after they moved.  With per-cell linked lists
-// that is list surgery; on the SoA it is a device counting sort by cell index (j-major, i-minor: the reference's
-// traversal order, IB:7106) followed by ONE launch that gathers every field into a second set of arrays, which then
-// becomes the SoA.  Dead bergs sort to the end and are dropped.  The order inside a cell is arbitrary (the bonded /
-// MTS path, where it matters, builds its own order every step and never re-bins); KID_STABLE_RESORT=1 in the
-// environment selects a stable comparison sort instead.
-// Correctness never depends on it (the kernels accept any order); speed does: the hot build shares LDS cell
-// packets and atomics between the lanes of a wave that sit in the same cell.
-// Is a step of this handle ONE plain hot build over the whole population (kid_step_local's default family -> launch_phase with
-// evolve | thermo | spread, kid_launch.inc)?  Only then can the copy of a re-binning wait for the step: asked when the re-binning is planned,
-// at the head of kid_step_local and by launch_phase itself.  The slow-lane schedule (it re-bins inside the step, with the
-// copy), the two-halves schedule and reproducible sums keep the eager copy; so does a decomposed run, which packs its
-// emigrants right after the re-binning.
-static bool rebin_fusable(const kid_handle *h) {
-  const kid_params &p = h->params;
-  return !h->dbg.rebin_eager && !h->repro && !h->mig_mode && !h->pipelined && h->have_forcing && p.Runge_not_Verlet && p.old_interp_flds_order &&
-         !p.static_icebergs && !p.mts && !p.interactive_icebergs_on && !p.footloose && !p.find_melt_using_spread_mass && !lanes_eligible(h) && plain_namelist(h);
-}
-int kid_move_berg_between_cells(kid_handle *h) {
-  if (!h) return KID_EINVAL;
-  { const int rc_h = halo_rows_refuse(h, "kid_move_berg_between_cells"); if (rc_h) return rc_h; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc_j = lanes_drain(h); if (rc_j) return rc_j; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (re-binning twice in a row: the second one sorts the rows of the first)
-  h->steps_since_sort = 0;
-  if (h->n == 0) return KID_OK;
-  if (h->have_bonds) { h->err = "bergs with bonds keep their rows: no re-binning while bond tables exist"; return KID_EUNSUPPORTED; }
-  int rc = rebin_plan(h);
-  if (rc) return rc;
-  if (rebin_fusable(h)) h->rebin_pending = true;
-  else { rc = rebin_apply(h, false, nullptr, nullptr); if (rc) return rc; }
-  // the dead sorted to the tail; they are dropped the next time the host asks for the count (no synchronisation here)
-  h->tail_valid = true;
-  return KID_OK;
-}
-// with_lane: the lane array moves with the rows and `list` (row numbers, *list_count of them) is translated
-static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count) {
-  const int rc = rebin_plan(h);
-  return rc ? rc : rebin_apply(h, with_lane, list, list_count);
-}
-// plan: the permutation (h->rplan.perm: source row of every destination row; its inverse in d_idx[0]) and the fields that move
-static int rebin_plan(kid_handle *h) {
-  h->static_rows_n = -1;   // rows move: the cached traversal order (mts_build_order) is of the old rows
-  const bool carry_repro = h->rp.srows_n == h->n;   // ... the one of reproducible sums is carried through (translate_rows_kernel)
-  h->rp.srows_n = -1;
-  const long long n = h->n;
-  const unsigned nb = (unsigned)((n + 255) / 256);
-  const unsigned dead_key = (unsigned)h->ncell;  // larger than any cell index
-  if (!h->d_key[0]) {
-    h->stable_resort = h->dbg.stable_resort;  // a stable comparison sort keeps the row order inside a cell
-    for (unsigned **q : {&h->d_key[0], &h->d_key[1], &h->d_idx[0], &h->d_idx[1]}) KID_HIP(h, h->mem.dev(*q, (size_t)h->capacity));
-    size_t tmp = 0;
-    KID_HIP(h, rocprim::radix_sort_pairs(nullptr, tmp, h->d_key[0], h->d_key[1], h->d_idx[0], h->d_idx[1], (size_t)h->capacity, 0u, 32u, h->stream));
-    KID_HIP(h, h->mem.reserve(h->sort_tmp, tmp));
-    KID_HIP(h, h->mem.dev(h->d_cell_hist, (size_t)h->ncell + 1));
-    tmp = 0;
-    KID_HIP(h, rocprim::exclusive_scan(nullptr, tmp, h->d_cell_hist, h->d_cell_hist, 0u, (size_t)h->ncell + 1, rocprim::plus<unsigned>(), h->stream));
-    KID_HIP(h, h->mem.reserve(h->cscan_tmp, tmp));
-    for (auto &field : h->bp_alt.f) KID_HIP(h, h->mem.dev(field, (size_t)h->capacity));
-    for (auto &field : h->bp_alt.i) KID_HIP(h, h->mem.dev(field, (size_t)h->capacity));
-    KID_HIP(h, h->mem.dev(h->bp_alt.id, (size_t)h->capacity));
-  }
-  const int32_t *live = nullptr;   // alive, or alive + waiting to be packed (decomposed runs): those keep their cell as key
-  { const int rc_l = layout_flags(h, &live); if (rc_l) return rc_l; }
-  const unsigned *perm = nullptr;
-  if (h->stable_resort) {
-    unsigned bits = 1; while ((1ull << bits) <= (unsigned long long)dead_key) ++bits;
-    hipLaunchKernelGGL(cell_key_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.i[KID_BI_INE], h->bp.i[KID_BI_JNE], live,
-                       h->gd.isd, h->gd.jsd, h->ni, dead_key, h->d_key[0], h->d_idx[0], n);
-    size_t tmp = h->sort_tmp.bytes;
-    KID_HIP(h, rocprim::radix_sort_pairs(h->sort_tmp.p, tmp, h->d_key[0], h->d_key[1], h->d_idx[0], h->d_idx[1], (size_t)n, 0u, bits, h->stream));
-    perm = h->d_idx[1];
-  } else {
-    KID_HIP(h, hipMemsetAsync(h->d_cell_hist, 0, ((size_t)h->ncell + 1) * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(cell_rank_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp.i[KID_BI_INE], h->bp.i[KID_BI_JNE], live,
-                       h->gd.isd, h->gd.jsd, h->ni, dead_key, h->d_key[0], h->d_key[1], h->d_cell_hist, n);
-    size_t tmp = h->cscan_tmp.bytes;
-    KID_HIP(h, rocprim::exclusive_scan(h->cscan_tmp.p, tmp, h->d_cell_hist, h->d_cell_hist, 0u, (size_t)h->ncell + 1, rocprim::plus<unsigned>(), h->stream));
-    hipLaunchKernelGGL(cell_place_kernel, dim3(nb), dim3(256), 0, h->stream, h->d_key[0], h->d_key[1], h->d_cell_hist, h->d_idx[1], h->d_idx[0], n);
-    perm = h->d_idx[1];
-    if (carry_repro) { hipLaunchKernelGGL(translate_rows_kernel, dim3(nb), dim3(256), 0, h->stream, h->rp.srows, (const unsigned *)h->d_idx[0], n); h->rp.srows_n = n; }
-  }
-  kid_handle::RebinPlan &pl = h->rplan;
-  pl = kid_handle::RebinPlan{};
-  PermTable &t = pl.t;
-  for (int f = 0; f < KID_NB_F64; ++f) {
-    if (!h->uploaded_nonzero[f] && field_never_written(h, f)) continue;  // all zeros, before and after
-    t.src[t.n8] = h->bp.f[f]; t.dst[t.n8] = h->bp_alt.f[f]; ++t.n8; pl.moved_f[pl.nmf++] = f; pl.moved |= 1ull << f;
-  }
-  t.src[t.n8] = h->bp.id; t.dst[t.n8] = h->bp_alt.id; ++t.n8;
-  for (int f = 0; f < KID_NB_I32; ++f) { t.src[t.n8 + t.n4] = h->bp.i[f]; t.dst[t.n8 + t.n4] = h->bp_alt.i[f]; ++t.n4; }
-  pl.perm = perm; pl.n = n;
-  KID_HIP(h, hipGetLastError());
-  return KID_OK;
-}
-// the planned rows change places on the host: the second set of arrays becomes the SoA; the device's pointer table follows
-static int rebin_swap(kid_handle *h) {
-  const kid_handle::RebinPlan &pl = h->rplan;
-  for (int q = 0; q < pl.nmf; ++q) std::swap(h->bp.f[pl.moved_f[q]], h->bp_alt.f[pl.moved_f[q]]);
-  std::swap(h->bp.id, h->bp_alt.id);
-  for (int f = 0; f < KID_NB_I32; ++f) std::swap(h->bp.i[f], h->bp_alt.i[f]);
-  if (h->tables_dirty) return refresh_tables(h);
-  // only the field pointers changed: one table, not four (a launch on the side stream may still be reading it)
-  { const int rc = join_side(h); if (rc) return rc; }
-  hipLaunchKernelGGL(set_berg_table_kernel, dim3(1), dim3(64), 0, h->stream, h->bp, h->d_bp);
-  KID_HIP(h, hipGetLastError());
-  return KID_OK;
-}
-// apply: ONE launch gathers every moving field into the second set of arrays
-static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count) {
-  PermTable t = h->rplan.t;
-  const long long n = h->rplan.n;
-  const unsigned nb = (unsigned)((n + 255) / 256);
-  if (with_lane) {
-    if (h->stable_resort) { h->err = "KID_STABLE_RESORT has no inverse permutation for the slow-lane re-binning"; return KID_EUNSUPPORTED; }
-    if (!h->d_lane_alt) KID_HIP(h, h->mem.dev(h->d_lane_alt, (size_t)h->capacity, 0));
-    t.src[t.n8 + t.n4] = h->d_lane; t.dst[t.n8 + t.n4] = h->d_lane_alt; ++t.n4;
-  }
-  hipLaunchKernelGGL(permute_all_kernel, dim3(nb), dim3(256), 0, h->stream, t, h->rplan.perm, n);
-  if (with_lane) {
-    std::swap(h->d_lane, h->d_lane_alt);
-    if (list) hipLaunchKernelGGL(translate_list_kernel, dim3(64), dim3(256), 0, h->stream, list, list_count, h->d_idx[0]);
-  }
-  KID_HIP(h, hipGetLastError());
-  return rebin_swap(h);
-}
-static int rebin_flush(kid_handle *h) {
-  if (!h->rebin_pending) return KID_OK;
-  h->rebin_pending = false;
-  KID_HIP(h, hipSetDevice(h->device));
-  return rebin_apply(h, false, nullptr, nullptr);
-}
-// The table of the re-binning instance of the plain hot build K for the pending plan.  The moved fields that build does not
-// write itself are head copies (KID_RB_NX8 with the id; the int32 fields always fit); what is left over is `surplus`.
-static bool rebin_table(const kid_handle *h, int K, RebinTab &tab) {
-  const kid_handle::RebinPlan &pl = h->rplan;
-  tab = RebinTab{};
-  tab.dst = h->bp;
-  for (int q = 0; q < pl.nmf; ++q) tab.dst.f[pl.moved_f[q]] = h->bp_alt.f[pl.moved_f[q]];
-  tab.dst.id = h->bp_alt.id;
-  for (int f = 0; f < KID_NB_I32; ++f) tab.dst.i[f] = h->bp_alt.i[f];
-  tab.moved = pl.moved;
-  const unsigned long long own = KID_RB_DYN | rb_thermo_fields(K);
-  for (int q = 0; q < pl.nmf; ++q) {
-    const int f = pl.moved_f[q];
-    if ((own >> f) & 1ull) continue;
-    if (tab.n8 >= KID_RB_NX8 - 1) { tab.surplus |= 1ull << f; continue; }
-    tab.xs[tab.n8] = h->bp.f[f]; tab.xd[tab.n8] = h->bp_alt.f[f]; ++tab.n8;
-  }
-  tab.xs[tab.n8] = h->bp.id; tab.xd[tab.n8] = h->bp_alt.id; ++tab.n8;
-  static_assert(KID_NB_I32 - 2 <= KID_RB_NX4, "every int32 field but the cell is a head copy");
-  for (int f = 0; f < KID_NB_I32; ++f) {
-    if (f == KID_BI_INE || f == KID_BI_JNE) continue;
-    tab.xs[KID_RB_NX8 + tab.n4] = h->bp.i[f]; tab.xd[KID_RB_NX8 + tab.n4] = h->bp_alt.i[f]; ++tab.n4;
-  }
-  return true;
-}
-int kid_set_resort_interval(kid_handle *h, int steps) {
-  if (!h || steps < 0) return KID_EINVAL;
-  h->resort_interval = steps;
-  return KID_OK;
-}
 
 // With .not.old_interp_flds_order the stored environment (berg%uo ... od) is an input of evolve_icebergs and thermodynamics as
 // the reference calls them, one after the other; the fused step (kid_run_step / kid_step_local) interpolates it for itself
@@ -1194,6 +783,7 @@ static int fl_assign_ids(kid_handle *h, long long n_old, int m) {
   KID_HIP(h, hipGetLastError());
   return KID_OK;
 }
+static const char *const fl_full = "footloose calving ran out of capacity: create the handle with room for child bergs";
 int kid_footloose_calving(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_footloose_calving"); if (rc_h) return rc_h; }
@@ -1214,17 +804,14 @@ int kid_footloose_calving(kid_handle *h) {
   int appended = 0;  // the population grew: the host needs the new size before the next launch
   KID_HIP(h, hipMemcpyAsync(&appended, h->d_fl_cursor, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   KID_HIP(h, hipStreamSynchronize(h->stream));
-  const int64_t room = h->capacity - h->n;
-  if (appended > room) {
-    h->n = h->capacity;
-    h->err = "footloose calving ran out of capacity: create the handle with room for child bergs";
-    return KID_ECAPACITY;
+  // the children become rows only once they are placed and have their ids: after a failure of either helper the population is
+  // what it was before the call
+  if (appended <= h->capacity - h->n) {
+    rc = fl_place_children(h, h->n, appended, fl_step_now);
+    if (!rc) rc = fl_assign_ids(h, h->n, appended);
+    if (rc) return rc;
   }
-  rc = fl_place_children(h, h->n, appended, fl_step_now);
-  if (rc) return rc;
-  rc = fl_assign_ids(h, h->n, appended);
-  h->n += appended;
-  return rc;
+  return rows_appended(h, appended, nullptr, fl_full);
 }
 double kid_footloose_uniform(int32_t seed, int64_t berg_id, int64_t step, int32_t draw) {   // the number a child placement uses (host side of kid_rng.h)
   return kid_fl_uniform((uint32_t)seed, berg_id, (uint32_t)step, (uint32_t)draw);

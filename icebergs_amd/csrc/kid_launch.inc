@@ -187,7 +187,7 @@ static int launch_phase(kid_handle *h, long long range_k0 = 0, long long range_l
   if (!rc) rc = refresh_tables(h);
   if (rc) return rc;
   const BergLaunch c = berg_launch(h);
-  h->tail_valid = false;
+  rows_killed(h);
   if (h->flags.store_env || !old) h->env_ever_stored = true;
   const bool stage = (PH & PH_SCATTER) != 0 && h->repro;   // the staging instance (kid_repro.inc); one part, no pipelining
   const int nparts = launch_parts(h->pipelined, stage, h->params.mts != 0, h->params.footloose != 0, (long long)h->n, range_len < 0);
@@ -238,7 +238,7 @@ static int launch_berg_lanes(kid_handle *h) {
   const BergLaunch c = berg_launch(h);
   hipStream_t M = h->stream, S = h->side_stream;
   const int s = h->lane_step, par = s & 1;
-  h->tail_valid = false;
+  rows_killed(h);
   if (h->flags.store_env || !OLDV) h->env_ever_stored = true;
   h->lanes_active = true;
   for (int q = 0; q < 2; ++q) if (h->evG_live[q] && h->pipelined) { KID_HIP(h, hipStreamWaitEvent(M, h->evG[q], 0)); h->evG_live[q] = false; }
@@ -338,14 +338,12 @@ static int step_footloose_fused(kid_handle *h) {
   int appended = 0;  // the population grew: the host needs the new size before the next launch
   KID_HIP(h, hipMemcpyAsync(&appended, h->d_fl_cursor, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   KID_HIP(h, hipStreamSynchronize(h->stream));
-  if (appended > h->capacity - n_old) {
-    h->n = h->capacity;
-    h->err = "footloose calving ran out of capacity: create the handle with room for child bergs";
-    return KID_ECAPACITY;
+  if (appended <= h->capacity - n_old) {
+    rc = fl_place_children(h, n_old, appended, fl_step_now);
+    if (!rc) rc = fl_assign_ids(h, n_old, appended);
+    if (rc) return rc;
   }
-  h->n = n_old + appended;
-  rc = fl_place_children(h, n_old, appended, fl_step_now);
-  if (!rc) rc = fl_assign_ids(h, n_old, appended);
+  rc = rows_appended(h, appended, nullptr, fl_full);
   return rc ? rc : launch_ordered<PH_THERMO | PH_SPREAD>(h, n_old, appended);
 }
 // phase by phase (KID_FL_UNFUSED, static bergs): three launches.  static_icebergs: evolve_icebergs is not called

@@ -10,8 +10,8 @@
 // A berg that leaves the computational domain is marked dead by the step with its post-evolve state stored (what
 // send_bergs_to_other_pes would pack before thermodynamics runs, IB:5404-5413); kid_pack_emigrants collects those rows and
 // moves their cell index back inside so that they are not sent twice.
+// The record itself -- MIG_WIDTH words, their order, kinds and members -- is WIRE_RECORD in kid_rows_plan.hpp.
 namespace {
-enum { MIG_WIDTH = 34 };
 struct MigSel { int dir[2], isc, iec, jsc, jec, has_halo; };   // dir[1] < 0: one direction; has_halo: some row may hold halo_berg != 0
 struct MigOut { double *buf[2]; long long cap[2]; };
 __device__ __forceinline__ int mig_selected(const MigSel &s, const BergPtrs &b, long long k) {   // 0 / 1: leaves through dir[0] / dir[1]; -1: stays
@@ -27,20 +27,29 @@ __device__ __forceinline__ int mig_selected(const MigSel &s, const BergPtrs &b, 
 }
 // pack_berg_into_buffer2 without bonds, FW:3268-3301: one record.  `halo` goes where halo_berg goes: the row's own for an
 // emigrant, 1 for the copy update_halo_icebergs sends (FW:1903-1906)
+template <int W> __device__ __forceinline__ double wire_word_of(const BergPtrs &b, long long k, double halo) {
+  constexpr WireWord ww = WIRE_RECORD[W];
+  if constexpr (W == WIRE_W_HALO_BERG) return halo;
+  else if constexpr (ww.kind == WIRE_F64) return b.f[ww.field][k];
+  else if constexpr (ww.kind == WIRE_ID_HI) return (double)(int32_t)(b.id[k] >> 32);                 // split_id, FW:3297-3299
+  else if constexpr (ww.kind == WIRE_ID_LO) return (double)(int32_t)(b.id[k] & 0xffffffffll);
+  else return (double)b.i[ww.field][k];                                                              // integers as reals
+}
+template <int... W> __device__ __forceinline__ void mig_write_words(double *o, const BergPtrs &b, long long k, double halo, std::integer_sequence<int, W...>) {
+  ((o[W] = wire_word_of<W>(b, k, halo)), ...);
+}
 __device__ __forceinline__ void mig_write_record(double *o, const BergPtrs &b, long long k, double halo) {
-  const int64_t id = b.id[k];
-  int c = 0;
-  o[c++] = b.f[KID_B_LON][k]; o[c++] = b.f[KID_B_LAT][k]; o[c++] = b.f[KID_B_UVEL][k]; o[c++] = b.f[KID_B_VVEL][k];
-  o[c++] = b.f[KID_B_UVEL_PREV][k]; o[c++] = b.f[KID_B_VVEL_PREV][k]; o[c++] = b.f[KID_B_XI][k]; o[c++] = b.f[KID_B_YJ][k];
-  o[c++] = b.f[KID_B_START_LON][k]; o[c++] = b.f[KID_B_START_LAT][k]; o[c++] = (double)b.i[KID_BI_START_YEAR][k]; o[c++] = b.f[KID_B_START_DAY][k];
-  o[c++] = b.f[KID_B_START_MASS][k]; o[c++] = b.f[KID_B_MASS][k]; o[c++] = b.f[KID_B_THICKNESS][k]; o[c++] = b.f[KID_B_WIDTH][k];
-  o[c++] = b.f[KID_B_LENGTH][k]; o[c++] = b.f[KID_B_FL_K][k]; o[c++] = b.f[KID_B_MASS_SCALING][k]; o[c++] = b.f[KID_B_MASS_OF_BITS][k];
-  o[c++] = b.f[KID_B_MASS_OF_FL_BITS][k]; o[c++] = b.f[KID_B_MASS_OF_FL_BERGY_BITS][k]; o[c++] = b.f[KID_B_HEAT_DENSITY][k];
-  o[c++] = (double)b.i[KID_BI_INE][k]; o[c++] = (double)b.i[KID_BI_JNE][k];
-  o[c++] = b.f[KID_B_AXN][k]; o[c++] = b.f[KID_B_AYN][k]; o[c++] = b.f[KID_B_BXN][k]; o[c++] = b.f[KID_B_BYN][k];
-  o[c++] = halo; o[c++] = b.f[KID_B_STATIC_BERG][k];
-  o[c++] = (double)(int32_t)(id >> 32); o[c++] = (double)(int32_t)(id & 0xffffffffll);                                   // split_id, FW:3297-3299
-  o[c++] = b.f[KID_B_OD][k];
+  mig_write_words(o, b, k, halo, std::make_integer_sequence<int, MIG_WIDTH>{});
+}
+// the members a record carries, into row k: unpack_berg_from_buffer2's pulls (FW:3503-3541) but for the cell and the position
+// inside it, which the receiving grid decides, and the id
+template <int W> __device__ __forceinline__ void wire_word_into(const BergPtrs &b, long long k, const double *r) {
+  constexpr WireWord ww = WIRE_RECORD[W];
+  if constexpr (ww.kind == WIRE_F64 && ww.field != KID_B_XI && ww.field != KID_B_YJ) b.f[ww.field][k] = r[W];
+  else if constexpr (ww.kind == WIRE_I32) b.i[ww.field][k] = (int)rint(r[W]);                        // nint, FW:3421
+}
+template <int... W> __device__ __forceinline__ void mig_read_words(const BergPtrs &b, long long k, const double *r, std::integer_sequence<int, W...>) {
+  (wire_word_into<W>(b, k, r), ...);
 }
 }  // namespace
 
@@ -50,15 +59,10 @@ __device__ __forceinline__ void mig_write_record(double *o, const BergPtrs &b, l
 __global__ void __launch_bounds__(256) pack_emigrants_kernel(const BergPtrs b, const MigSel s, long long n, unsigned long long *cursor, const MigOut out) {
   const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
   const int which = k < n ? mig_selected(s, b, k) : -1;
-  const int lane = (int)__lane_id();
   long long slot = -1;
   for (int q = 0; q < 2; ++q) {   // one reservation per wave and direction
-    const unsigned long long m = __ballot(which == q);
-    if (!m) continue;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(cursor + q, (unsigned long long)__popcll(m));
-    base = __shfl(base, 0);
-    if (which == q) slot = (long long)base + __popcll(m & ((1ull << lane) - 1ull));
+    const long long mine = wave_reserve(which == q, cursor + q);
+    if (which == q) slot = mine;
   }
   if (which < 0 || slot >= out.cap[which]) return;
   mig_write_record(out.buf[which] + (size_t)slot * MIG_WIDTH, b, k, b.f[KID_B_HALO_BERG][k]);
@@ -81,19 +85,12 @@ __global__ void __launch_bounds__(64) unpack_immigrants_kernel(const DevGrid g, 
   // the order of the pulls, FW:3503-3541; everything a record does not carry starts from zero
   for (int f = 0; f < KID_NB_F64; ++f) b.f[f][k] = 0.;
   for (int f = 0; f < KID_NB_I32; ++f) b.i[f][k] = 0;
-  const double x = r[0], y = r[1];
-  b.f[KID_B_LON][k] = x; b.f[KID_B_LAT][k] = y; b.f[KID_B_UVEL][k] = r[2]; b.f[KID_B_VVEL][k] = r[3];
-  b.f[KID_B_UVEL_PREV][k] = r[4]; b.f[KID_B_VVEL_PREV][k] = r[5];
-  b.f[KID_B_START_LON][k] = r[8]; b.f[KID_B_START_LAT][k] = r[9]; b.i[KID_BI_START_YEAR][k] = (int)rint(r[10]); b.f[KID_B_START_DAY][k] = r[11];   // nint, FW:3421
-  b.f[KID_B_START_MASS][k] = r[12]; b.f[KID_B_MASS][k] = r[13]; b.f[KID_B_THICKNESS][k] = r[14]; b.f[KID_B_WIDTH][k] = r[15];
-  b.f[KID_B_LENGTH][k] = r[16]; b.f[KID_B_FL_K][k] = r[17]; b.f[KID_B_MASS_SCALING][k] = r[18]; b.f[KID_B_MASS_OF_BITS][k] = r[19];
-  b.f[KID_B_MASS_OF_FL_BITS][k] = r[20]; b.f[KID_B_MASS_OF_FL_BERGY_BITS][k] = r[21]; b.f[KID_B_HEAT_DENSITY][k] = r[22];
-  b.f[KID_B_AXN][k] = r[25]; b.f[KID_B_AYN][k] = r[26]; b.f[KID_B_BXN][k] = r[27]; b.f[KID_B_BYN][k] = r[28];
-  b.f[KID_B_HALO_BERG][k] = r[29]; b.f[KID_B_STATIC_BERG][k] = r[30]; b.f[KID_B_OD][k] = r[33];
-  b.id[k] = (int64_t)(((uint64_t)(uint32_t)(int32_t)rint(r[31]) << 32) | (uint64_t)(uint32_t)(int32_t)rint(r[32]));   // id_from_2_ints
-  b.f[KID_B_UVEL_OLD][k] = r[2]; b.f[KID_B_VVEL_OLD][k] = r[3]; b.f[KID_B_LON_OLD][k] = x; b.f[KID_B_LAT_OLD][k] = y;   // FW:3573-3577
+  const double x = r[WIRE_W_LON], y = r[WIRE_W_LAT];
+  mig_read_words(b, k, r, std::make_integer_sequence<int, MIG_WIDTH>{});
+  b.id[k] = (int64_t)(((uint64_t)(uint32_t)(int32_t)rint(r[WIRE_W_ID_HI]) << 32) | (uint64_t)(uint32_t)(int32_t)rint(r[WIRE_W_ID_LO]));   // id_from_2_ints
+  b.f[KID_B_UVEL_OLD][k] = r[WIRE_W_UVEL]; b.f[KID_B_VVEL_OLD][k] = r[WIRE_W_VVEL]; b.f[KID_B_LON_OLD][k] = x; b.f[KID_B_LAT_OLD][k] = y;   // FW:3573-3577
   b.i[KID_BI_ALIVE][k] = 1;
-  int i = (int)rint(r[23]), j = (int)rint(r[24]);
+  int i = (int)rint(r[WIRE_W_INE]), j = (int)rint(r[WIRE_W_JNE]);
   auto holds = [&](int ii, int jj) { return cell_in_data_domain(g, ii, jj) && is_point_in_cell<false>(g, GlbCell{g, g.idx(ii, jj)}.corners(), x, y); };
   bool found = holds(i, j);
   if (!found) {
@@ -107,8 +104,8 @@ __global__ void __launch_bounds__(64) unpack_immigrants_kernel(const DevGrid g, 
       for (int ii = g.isd + 1; ii <= g.ied && !found; ++ii)
         if (holds(ii, jj)) { i = ii; j = jj; found = true; }
   // the kernels trust cell indices up to one cell outside the computational domain (as kid_upload_bergs checks); a halo row
-  // (r[29] = 1, kid_halo_bergs.inc) sits anywhere in the data domain: only the cell tables of the interacting scheme see it
-  if (found && !(r[29] >= 0.5) && (i < g.isc - 1 || i > g.iec + 1 || j < g.jsc - 1 || j > g.jec + 1)) found = false;
+  // (halo_berg = 1, kid_halo_bergs.inc) sits anywhere in the data domain: only the cell tables of the interacting scheme see it
+  if (found && !(r[WIRE_W_HALO_BERG] >= 0.5) && (i < g.isc - 1 || i > g.iec + 1 || j < g.jsc - 1 || j > g.jec + 1)) found = false;
   if (!found) { atomicAdd(nerr, 1); b.i[KID_BI_ALIVE][k] = 0; b.i[KID_BI_INE][k] = g.isc; b.i[KID_BI_JNE][k] = g.jsc; return; }
   double xi = 0., yj = 0.;
   int err = 0; bool bail = false;
@@ -146,6 +143,47 @@ static int mig_stage(kid_handle *h, long long rows) {   // host-visible staging 
   return KID_OK;
 }
 
+// One pack pass through the staging buffer, for kid_pack_emigrants* and kid_pack_halo_bergs_pair.  launch(out) enqueues the
+// caller's kernel, which counts every selected row of direction q on h->d_count[q] and writes the first out.cap[q] records.
+// The staging is sized from what the previous calls carried (`last`), not from the caller's capacities (a host passes its
+// whole obuffer, n_slots x 272 B per direction): a pass that finds more than fit counts them all and is repeated once with
+// room for the count; the source rows are only read, so nothing is lost.  One host read per pass.  *n[q] (where given) is the
+// count; `packed`: the records are in buf[].  A caller's buffer smaller than its count: nothing is copied, KID_ECAPACITY.
+}  // extern "C"
+template <class Launch>
+static int pack_staged(kid_handle *h, int nd, double *const *buf, const int64_t *capacity, int64_t *const *n, long long *last, const char *too_small, Launch launch, bool &packed) {
+  packed = false;
+  long long sc[2] = {0, 0}, cnt[2] = {0, 0};
+  for (int q = 0; q < nd; ++q) sc[q] = std::min<long long>((long long)capacity[q], std::max<long long>(4096, 2 * last[q]));
+  MigOut out{};
+  bool fits = true, any = false;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    { const int rc = mig_stage(h, sc[0] + sc[1]); if (rc) return rc; }
+    out = MigOut{{h->d_mig_buf, h->d_mig_buf + (size_t)sc[0] * MIG_WIDTH}, {sc[0], sc[1]}};
+    KID_HIP(h, hipMemsetAsync(h->d_count, 0, 2 * sizeof(unsigned long long), h->stream));
+    launch(out);
+    KID_HIP(h, hipGetLastError());
+    KID_HIP(h, hipMemcpyAsync(mig_pinned_word(h), h->d_count, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    KID_HIP(h, hipStreamSynchronize(h->stream));
+    fits = true; any = false;
+    bool staged = true;
+    for (int q = 0; q < nd; ++q) {
+      const long long c = cnt[q] = (long long)mig_pinned_word(h)[q];
+      if (n[q]) *n[q] = c;
+      last[q] = c;
+      fits = fits && c <= capacity[q]; any = any || c > 0; staged = staged && c <= sc[q];
+      sc[q] = std::min<long long>((long long)capacity[q], std::max<long long>(sc[q], c));
+    }
+    if (!any || !fits || staged) break;
+  }
+  if (!any) return KID_OK;
+  if (!fits) { h->err = too_small; return KID_ECAPACITY; }
+  for (int q = 0; q < nd; ++q) if (cnt[q] > 0) std::memcpy(buf[q], out.buf[q], (size_t)cnt[q] * MIG_WIDTH * sizeof(double));
+  packed = true;
+  return KID_OK;
+}
+extern "C" {
+
 static int pack_core(kid_handle *h, int nd, const int32_t *dir, double *const *buf, const int64_t *capacity, int64_t *const *n) {
   for (int q = 0; q < nd; ++q) {
     if (!n[q] || dir[q] < KID_DIR_E || dir[q] > KID_DIR_S || capacity[q] < 0 || (capacity[q] > 0 && !buf[q])) return KID_EINVAL;
@@ -153,46 +191,20 @@ static int pack_core(kid_handle *h, int nd, const int32_t *dir, double *const *b
   }
   { const int rc_h = halo_rows_refuse(h, "kid_pack_emigrants"); if (rc_h) return rc_h; }
   { const int rc = mig_supported(h); if (rc) return rc; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc = lanes_drain(h); if (rc) return rc; }   // a berg the slow lane still owes a step has not left yet
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }   // a berg the slow lane still owes a step has not left yet
   if (h->n == 0) return KID_OK;
   const MigSel s{{dir[0], nd > 1 ? dir[1] : -1}, h->gd.isc, h->gd.iec, h->gd.jsc, h->gd.jec, h->flags.has_static ? 1 : 0};
   const unsigned nb = (unsigned)((h->n + 255) / 256);
-  // The pinned staging buffer is sized from what the previous calls carried, not from the caller's capacities (a host passes
-  // its whole obuffer, n_slots x 272 B per direction): a pass that finds more leavers than fit counts them all, packs
-  // nothing that matters (nothing is deleted before every record has landed) and is repeated once with room for the count.
-  long long sc[2] = {0, 0};
-  for (int q = 0; q < nd; ++q) sc[q] = std::min<long long>((long long)capacity[q], std::max<long long>(4096, 2 * h->mig_last[q]));
-  MigOut out{};
-  bool fits = true, any = false;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    { const int rc = mig_stage(h, sc[0] + sc[1]); if (rc) return rc; }
-    out = MigOut{{h->d_mig_buf, h->d_mig_buf + (size_t)sc[0] * MIG_WIDTH}, {sc[0], sc[1]}};
-    // one pass and one host read: the records land in the staging buffer while they are counted
-    KID_HIP(h, hipMemsetAsync(h->d_count, 0, 2 * sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(pack_emigrants_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp, s, (long long)h->n, h->d_count, out);
-    KID_HIP(h, hipGetLastError());
-    KID_HIP(h, hipMemcpyAsync(mig_pinned_word(h), h->d_count, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    KID_HIP(h, hipStreamSynchronize(h->stream));
-    fits = true; any = false;
-    bool staged = true;
-    for (int q = 0; q < nd; ++q) {
-      const long long c = (long long)mig_pinned_word(h)[q];
-      *n[q] = c; h->mig_last[q] = c;
-      fits = fits && c <= capacity[q]; any = any || c > 0; staged = staged && c <= sc[q];
-      sc[q] = std::min<long long>((long long)capacity[q], std::max<long long>(sc[q], c));
-    }
-    if (!any || !fits || staged) break;
-  }
-  if (!any) return KID_OK;
-  if (!fits) { h->err = "kid_pack_emigrants: a buffer is too small (*n holds the bergs waiting); nothing was packed"; return KID_ECAPACITY; }
-  for (int q = 0; q < nd; ++q) if (*n[q] > 0) std::memcpy(buf[q], out.buf[q], (size_t)*n[q] * MIG_WIDTH * sizeof(double));
+  bool packed = false;   // nothing is deleted before every record has landed
+  const int rc = pack_staged(h, nd, buf, capacity, n, h->mig_last, "kid_pack_emigrants: a buffer is too small (*n holds the bergs waiting); nothing was packed",
+                             [&](const MigOut &out) { hipLaunchKernelGGL(pack_emigrants_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp, s, (long long)h->n, h->d_count, out); }, packed);
+  if (rc || !packed) return rc;
   hipLaunchKernelGGL(consume_emigrants_kernel, dim3(nb), dim3(256), 0, h->stream, h->bp, s, (long long)h->n);   // no wait: the stream orders it
   KID_HIP(h, hipGetLastError());
-  h->tail_valid = false;
+  rows_killed(h);
   return KID_OK;
 }
+
 
 int kid_pack_emigrants(kid_handle *h, int32_t dir, double *buf, int64_t capacity, int64_t *n) {
   if (!h) return KID_EINVAL;
@@ -214,12 +226,10 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   const int64_t m = m_a + m_b;
   if (m == 0) return KID_OK;
   bool any_halo = false;   // copies of a neighbour's bergs (update_halo_icebergs FW:1800-2131): only the scheme kid_halo_bergs.inc covers takes them
-  for (int64_t q = 0; q < m_a && !any_halo; ++q) any_halo = buf_a[(size_t)q * MIG_WIDTH + 29] >= 0.5;
-  for (int64_t q = 0; q < m_b && !any_halo; ++q) any_halo = buf_b[(size_t)q * MIG_WIDTH + 29] >= 0.5;
+  for (int64_t q = 0; q < m_a && !any_halo; ++q) any_halo = buf_a[(size_t)q * MIG_WIDTH + WIRE_W_HALO_BERG] >= 0.5;
+  for (int64_t q = 0; q < m_b && !any_halo; ++q) any_halo = buf_b[(size_t)q * MIG_WIDTH + WIRE_W_HALO_BERG] >= 0.5;
   if (any_halo) { const int rc = halo_bergs_supported(h, "kid_unpack_immigrants"); if (rc) return rc; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc = lanes_drain(h); if (rc) return rc; }
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }
   if (h->tail_valid) { int64_t slots = 0, alive = 0; const int rc = kid_num_bergs(h, &slots, &alive); if (rc) return rc; }   // drop a dead tail first (rows waiting to be packed are not part of it)
   if (h->n + m > h->capacity) {   // dead rows of earlier leavers and melted bergs pile up between re-binnings: reclaim them before refusing
     const int rc = kid_compact_bergs(h);
@@ -231,19 +241,6 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   KID_HIP(h, hipStreamSynchronize(h->stream));   // (a consume launch may still read nothing of it, but an earlier unpack kernel may)
   if (m_a > 0) std::memcpy(h->d_mig_buf, buf_a, (size_t)m_a * MIG_WIDTH * sizeof(double));   // rows in the order of the reference's two unpack loops
   if (m_b > 0) std::memcpy(h->d_mig_buf + (size_t)m_a * MIG_WIDTH, buf_b, (size_t)m_b * MIG_WIDTH * sizeof(double));
-  // which optional fields can matter from now on (kid_upload_bergs keeps the same books)
-  static const int wire_f64[MIG_WIDTH] = {KID_B_LON, KID_B_LAT, KID_B_UVEL, KID_B_VVEL, KID_B_UVEL_PREV, KID_B_VVEL_PREV, KID_B_XI, KID_B_YJ,
-    KID_B_START_LON, KID_B_START_LAT, -1 /* start_year */, KID_B_START_DAY, KID_B_START_MASS, KID_B_MASS, KID_B_THICKNESS, KID_B_WIDTH,
-    KID_B_LENGTH, KID_B_FL_K, KID_B_MASS_SCALING, KID_B_MASS_OF_BITS, KID_B_MASS_OF_FL_BITS, KID_B_MASS_OF_FL_BERGY_BITS, KID_B_HEAT_DENSITY,
-    -2 /* ine */, -3 /* jne */, KID_B_AXN, KID_B_AYN, KID_B_BXN, KID_B_BYN, KID_B_HALO_BERG, KID_B_STATIC_BERG, -4 /* id_cnt */, -5 /* id_ij */, KID_B_OD};
-  for (size_t q = 0; q < mm; ++q) {
-    const double *r = h->d_mig_buf + q * MIG_WIDTH;
-    for (int w = 0; w < MIG_WIDTH; ++w) if (wire_f64[w] >= 0 && r[w] != 0.) h->uploaded_nonzero[wire_f64[w]] = true;
-    if (r[30] != 0. || r[29] != 0.) h->flags.has_static = 1;
-    if (r[20] != 0. || r[21] != 0. || r[17] != 0.) h->flags.has_fl = 1;
-  }
-  h->uploaded_nonzero[KID_B_UVEL_OLD] |= h->uploaded_nonzero[KID_B_UVEL]; h->uploaded_nonzero[KID_B_VVEL_OLD] |= h->uploaded_nonzero[KID_B_VVEL];
-  h->uploaded_nonzero[KID_B_LON_OLD] |= h->uploaded_nonzero[KID_B_LON]; h->uploaded_nonzero[KID_B_LAT_OLD] |= h->uploaded_nonzero[KID_B_LAT];
   { const int rc = refresh_tables(h); if (rc) return rc; }
   // one launch decodes the records into rows n .. n + m - 1, finds the cells and the positions inside them; one host read
   KID_HIP(h, hipMemsetAsync(h->d_count, 0, sizeof(unsigned long long), h->stream));
@@ -253,10 +250,10 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
   KID_HIP(h, hipMemcpyAsync(mig_pinned_word(h), h->d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   KID_HIP(h, hipStreamSynchronize(h->stream));
   const int nerr = (int)(*mig_pinned_word(h) & 0xffffffffull);
-  h->n += m;
+  // room was made above, before anything was written: this cannot come back full.  The records tell which optional fields
+  // can matter from now on (kid_upload_bergs keeps the same books)
+  { const int rc = rows_appended(h, m, h->d_mig_buf, "kid_unpack_immigrants: out of capacity"); if (rc) return rc; }
   if (any_halo) h->halo_rows_live = true;
-  h->tail_valid = false; h->static_rows_n = -1; h->rp.srows_n = -1;
-  if (!h->params.old_interp_flds_order) h->env_ever_stored = true;
   if (nerr > 0) { h->err = "kid_unpack_immigrants: can not find a cell to place berg in! (" + std::to_string(nerr) + " bergs dropped)"; return KID_EINVAL; }
   return KID_OK;
 }

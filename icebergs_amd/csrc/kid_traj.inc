@@ -177,10 +177,8 @@ int kid_record_posn(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_record_posn"); if (rc_h) return rc_h; }
   if (!h->traj_on) { h->err = "kid_set_traj_params must be called first"; return KID_EINVAL; }
-  KID_HIP(h, hipSetDevice(h->device));
-  { const int rc = join_side(h); if (rc) return rc; }
+  { const int rc = rows_enter(h, ROWS_READ); if (rc) return rc; }
   if (h->n == 0) return KID_OK;
-  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   { const int rc = refresh_tables(h); if (rc) return rc; }
   int fields[KID_NTRAJ_VARS];
   h->traj_nf = traj_fields(h, fields);

@@ -90,7 +90,11 @@ int kid_set_forcing_device(kid_handle *h, const double *const dev_fields[KID_NFO
 int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host);        /* sets the population (n <= capacity) */
 int kid_download_bergs(kid_handle *h, kid_berg_soa *host);            /* host->n must be >= kid_num_bergs slots */
 int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive); /* slots include dead bergs until compaction */
-int kid_compact_bergs(kid_handle *h);                                 /* drop melted / departed bergs, keep order */
+/* Drops melted / departed bergs and keeps the order of the rest.  One gather of every field into the second set of arrays that
+ * the re-binning uses too: the first call of either allocates it (kid_memory_in_use then reports one more berg SoA for the
+ * handle).  While bond tables exist (kid_upload_bonds, kid_initialize_bonds) rows keep their places: KID_EUNSUPPORTED, as from
+ * kid_move_berg_between_cells, and nothing is changed. */
+int kid_compact_bergs(kid_handle *h);
 /* move_berg_between_cells (IB:5437): device counting sort of the SoA by cell (j-major), dead bergs dropped.  Results
  * never depend on it, speed does.  kid_run_step calls it every `steps` steps (default 16; 0 = never). */
 int kid_move_berg_between_cells(kid_handle *h);
@@ -286,6 +290,11 @@ int kid_zero_accumulators(kid_handle *h);
 int kid_interp_gridded_fields_to_bergs(kid_handle *h);
 int kid_evolve_icebergs(kid_handle *h);
 int kid_footloose_calving(kid_handle *h);
+/* kid_footloose_calving and the fused footloose step add the children to the population only once they are placed and have
+ * their ids.  After KID_EHIP from either the row count (kid_num_bergs) is what it was before the call and no child is part of
+ * the population; the parents have already shed the mass and the footloose step has advanced, so the handle is good for
+ * reading out, not for stepping on.  After KID_ECAPACITY the handle is full (n_slots = capacity) and the children beyond it
+ * were not written. */
 /* Footloose children are placed on their parent's perimeter (displace_fl_bergs, IB:2631, 2664, 6432-6498) with the
  * counter-based generator of include/kid_rng.h: rn = f(kid_params.fl_rng_seed, parent id, footloose step, draw).  The step
  * counts the footloose passes of this handle (0 at kid_create, +1 per kid_footloose_calving or fused footloose step);
