@@ -97,6 +97,7 @@ struct kid_handle {
   bool fl_place_warm = false;
   unsigned fl_step = 0;                  // footloose passes so far: third counter word of the child-placement generator (kid_rng.h)
   int *d_fl_cursor = nullptr;
+  int *d_fl_promoted = nullptr;          // kid_adjust_fl_berg_interactivity: children promoted by one pass, when the caller asks
   int32_t *d_fl_head = nullptr, *d_fl_next = nullptr; int64_t *d_fl_newid = nullptr; long long fl_ev_capacity = 0;   // fl_assign_ids_*
   unsigned *d_key[2] = {nullptr, nullptr}, *d_idx[2] = {nullptr, nullptr};  // radix-sort ping-pong buffers
   Scratch sort_tmp;

@@ -31,6 +31,7 @@
 #include "kid_footloose.hpp"
 #include "kid_berg_kernel.hpp"
 #include "kid_rows_plan.hpp"
+#include "kid_fl_contact.hpp"
 
 using namespace kid;
 
@@ -187,6 +188,7 @@ __global__ void set_time_kernel(int32_t year, double yearday, kid_params *dst) {
 __global__ void set_grid_kernel(const DevGrid src, DevGrid *dst) { if (threadIdx.x == 0 && blockIdx.x == 0) *dst = src; }
 
 #include "kid_mts.inc"
+#include "kid_fl_interact.inc"
 
 // -------------------------------------------------------------------------------------------------------
 // IB:6077-6150 sum_up_spread_fields + IB:3449-3488, per cell of the computational domain
@@ -328,7 +330,9 @@ static int check_params(kid_handle *h, const kid_params *p) {
     if (p->footloose) { h->err = "footloose together with mts is not implemented"; return KID_EUNSUPPORTED; }
   } else if (p->interactive_icebergs_on || p->iceberg_bonds_on) {
     if (p->Runge_not_Verlet) { h->err = "interacting / bonded bergs under the single-time-step scheme are implemented for Verlet only (Runge_not_Verlet=F)"; return KID_EUNSUPPORTED; }
-    if (p->footloose) { h->err = "footloose together with interacting bergs is not implemented"; return KID_EUNSUPPORTED; }
+    // footloose children among interacting bergs: kid_fl_interact.inc.  With bonds a bonded edge element that would calve is the
+    // reference's own FATAL (IB:2566-2569, 2585)
+    if (p->footloose && p->iceberg_bonds_on) { h->err = "footloose together with iceberg_bonds_on: bonded footloose calving (edge elements that calve, IB:2566-2585) is not implemented"; return KID_EUNSUPPORTED; }
     if (p->iceberg_bonds_on && !p->interactive_icebergs_on) { h->err = "iceberg_bonds_on without interactive_icebergs_on is not implemented"; return KID_EUNSUPPORTED; }
     if (p->max_bonds < 1 || p->max_bonds > KID_MAX_BONDS) { h->err = "max_bonds out of range"; return KID_EINVAL; }
   }

@@ -320,8 +320,13 @@ static int step_interactive(kid_handle *h) {   // single-time-step scheme with i
   int rc = h->visited ? KID_OK : sts_ia_first_visit(h);
   if (!rc && !p.old_interp_flds_order) rc = launch_berg<PH_INTERP>(h);
   if (!rc && !p.static_icebergs) rc = kid_evolve_icebergs_interactive(h);
+  // footloose: the children are rows before the conglomerates are labelled and owe this step's thermodynamics and spreading
+  // like everybody else (IB:5453); KID_ECAPACITY ends the step here, as it ends config 3's
+  if (!rc && p.footloose) rc = kid_footloose_calving(h);
   if (!rc && contact) rc = kid_set_conglom_ids(h);   // IB:5470-5471
   if (!rc) rc = bond_orientations(h);
+  // IB:5486 (the interpolation of IB:5473 in front of it is inside the launch below; the pass reads positions and sizes only)
+  if (!rc && p.footloose) rc = kid_adjust_fl_berg_interactivity(h, nullptr);
   return rc ? rc : launch_ordered<PH_THERMO | PH_SPREAD>(h);
 }
 // Footloose calving sits between evolve and thermodynamics (IB:5453): fused into the per-berg launch (PH_FL), one pass over

@@ -499,6 +499,36 @@ int kid_evolve_icebergs_interactive(kid_handle *h) {
   h->halo_rows_live = false;   // the position sweep has retired them
   return mts_fold_scalars(h);
 }
+// adjust_fl_berg_interactivity (IB:2765-2841, called at IB:5486): footloose children (fl_k = -1) out of everybody's contact
+// range become interactive (fl_k = -2).  The cell tables it walks are those of the contact searches; rows appended since they
+// were built -- the children of this step's kid_footloose_calving -- are sorted in first, as candidates and as partners.
+int kid_adjust_fl_berg_interactivity(kid_handle *h, int64_t *promoted) {
+  if (!h) return KID_EINVAL;
+  if (promoted) *promoted = 0;
+  { const int rc_h = halo_rows_refuse(h, "kid_adjust_fl_berg_interactivity"); if (rc_h) return rc_h; }
+  const kid_params &p = h->params;
+  if (!p.footloose || !p.interactive_icebergs_on || p.mts || h->n == 0) return KID_OK;
+  KID_HIP(h, hipSetDevice(h->device));
+  { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
+  int rc = mts_ensure_default(h);
+  if (!rc) rc = mts_build_order(h);   // (its own question -- has a row changed its cell, died, or been appended? -- decides whether anything is sorted)
+  if (!rc) rc = mts_refresh(h);
+  if (rc) return rc;
+  if (promoted) {
+    if (!h->d_fl_promoted) KID_HIP(h, h->mem.dev(h->d_fl_promoted, 1));
+    KID_HIP(h, hipMemsetAsync(h->d_fl_promoted, 0, sizeof(int), h->stream));
+  }
+  hipLaunchKernelGGL(fl_adjust_interactivity_kernel, MTS_GRID(h->n), dev_grid(h), (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp,
+                     (const MtsDev *)h->d_mts, (long long)h->n, promoted ? h->d_fl_promoted : nullptr);
+  KID_HIP(h, hipGetLastError());
+  if (promoted) {
+    int count = 0;
+    KID_HIP(h, hipMemcpyAsync(&count, h->d_fl_promoted, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    KID_HIP(h, hipStreamSynchronize(h->stream));
+    *promoted = (int64_t)count;
+  }
+  return KID_OK;
+}
 // the `Visited` block for interacting bergs without MTS (IB:5415-5418)
 static int sts_ia_first_visit(kid_handle *h) {
   const kid_params &p = h->params;

@@ -27,7 +27,7 @@ module kid_hip_mod
   public :: kid_pack_halo_bergs_pair, kid_halo_berg_count
   public :: kid_traj_params, kid_set_traj_params, kid_record_posn, kid_write_trajectories, kid_write_bond_trajectories
   public :: kid_zero_accumulators, kid_interp_gridded_fields_to_bergs, kid_evolve_icebergs, kid_footloose_calving
-  public :: kid_set_footloose_step, kid_get_footloose_step
+  public :: kid_set_footloose_step, kid_get_footloose_step, kid_adjust_fl_berg_interactivity
   public :: kid_thermodynamics, kid_create_gridded_icebergs_fields, kid_step_local, kid_step_gather, kid_run_step
   public :: kid_get_accumulators, kid_last_error_f, kid_check
   ! every entry point of include/kid.h is usable from Fortran (tests/test_abi.py checks the list against the header)
@@ -351,6 +351,11 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int64_t
       type(c_ptr), value :: h
       integer(c_int64_t), intent(out) :: step
+    end function
+    integer(c_int) function kid_adjust_fl_berg_interactivity(h, promoted) bind(C, name='kid_adjust_fl_berg_interactivity')  ! IB:5486
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+      type(c_ptr), value :: promoted   ! c_loc of an integer(c_int64_t), or c_null_ptr: nothing is read back
     end function
     integer(c_int) function kid_step_prepare(h, fields) bind(C, name='kid_step_prepare')
       import :: c_int, c_ptr

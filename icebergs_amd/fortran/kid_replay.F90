@@ -113,6 +113,8 @@ program kid_replay
       if (par%footloose /= 0) call kid_check(kid_footloose_calving(h), h, 'kid_footloose_calving') ! IB:5453
       if (par%old_interp_flds_order == 0) &
         call kid_check(kid_interp_gridded_fields_to_bergs(h), h, 'interp (2)')        ! IB:5473
+      if (par%footloose /= 0 .and. par%interactive_icebergs_on /= 0) &
+        call kid_check(kid_adjust_fl_berg_interactivity(h, c_null_ptr), h, 'kid_adjust_fl_berg_interactivity') ! IB:5486
       call kid_check(kid_thermodynamics(h), h, 'kid_thermodynamics')                ! IB:5505
       call kid_check(kid_create_gridded_icebergs_fields(h), h, 'kid_create_gridded_icebergs_fields') ! IB:5512
     end if

@@ -515,6 +515,13 @@ class Icebergs:
         self._check(self.lib.kid_get_footloose_step(self.h, C.byref(s)), "kid_get_footloose_step")
         return int(s.value)
 
+    def adjust_fl_berg_interactivity(self):
+        """adjust_fl_berg_interactivity (IB:5486): footloose children (fl_k = -1) that no other berg is in contact range of become
+        interactive (fl_k = -2); returns how many did.  Nothing happens unless footloose and interactive_icebergs_on are both on."""
+        n = C.c_int64(0)
+        self._check(self.lib.kid_adjust_fl_berg_interactivity(self.h, C.byref(n)), "kid_adjust_fl_berg_interactivity")
+        return int(n.value)
+
     def set_iceberg_counter(self, counter):
         a = np.ascontiguousarray(counter, dtype=np.int32)
         assert a.shape == (self.nj, self.ni)

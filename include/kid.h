@@ -18,6 +18,7 @@
  *   evolve_icebergs                       IB:5433          kid_evolve_icebergs
  *   move_berg_between_cells               IB:5437          kid_move_berg_between_cells
  *   footloose_calving                     IB:5453          kid_footloose_calving
+ *   adjust_fl_berg_interactivity          IB:5486          kid_adjust_fl_berg_interactivity
  *   thermodynamics                        IB:5505          kid_thermodynamics
  *   create_gridded_icebergs_fields        IB:5512          kid_create_gridded_icebergs_fields
  *   (all of the above, one coupling step)                  kid_run_step / kid_step_local + kid_step_gather
@@ -237,8 +238,8 @@ int kid_unpack_immigrants_pair(kid_handle *h, const double *buf_a, int64_t n_a, 
  * A halo row is a force source for that one kid_evolve_icebergs: its velocity sweep skips the row, its position sweep retires it
  * (dead, its cell put back inside; the next compaction or re-binning drops it).  From the unpack to that evolve
  * kid_interp_gridded_fields_to_bergs, kid_thermodynamics, the spreading and gather calls, kid_step_local, kid_run_step,
- * kid_budget, kid_stock, kid_incr_mass, kid_pack_emigrants*, kid_move_berg_between_cells, kid_footloose_calving, kid_calving,
- * kid_write_restart, kid_bergs_chksum, kid_record_posn and kid_write_trajectories return KID_EINVAL.  The reference takes the copies before thermodynamics (IB:5462)
+ * kid_budget, kid_stock, kid_incr_mass, kid_pack_emigrants*, kid_move_berg_between_cells, kid_footloose_calving,
+ * kid_adjust_fl_berg_interactivity, kid_calving, kid_write_restart, kid_bergs_chksum, kid_record_posn and kid_write_trajectories return KID_EINVAL.  The reference takes the copies before thermodynamics (IB:5462)
  * and uses them in the next step's evolve; these calls do not fix the moment.
  * Covered: interactive_icebergs_on under the single-time-step Verlet scheme without bonds.  iceberg_bonds_on, mts, dem,
  * footloose, find_melt_using_spread_mass, static_icebergs, periodic_reentry, a namelist without interactive_icebergs_on and Runge_not_Verlet:
@@ -302,6 +303,22 @@ int kid_footloose_calving(kid_handle *h);
 double kid_footloose_uniform(int32_t seed, int64_t berg_id, int64_t step, int32_t draw);   /* the generator, for hosts that want to check a placement */
 int kid_set_footloose_step(kid_handle *h, int64_t step);
 int kid_get_footloose_step(kid_handle *h, int64_t *step);
+/* adjust_fl_berg_interactivity (IB:2765-2841, called at IB:5486), for footloose together with interactive_icebergs_on under the
+ * single-time-step Verlet scheme (no bonds, no mts).  A footloose child is born with fl_k = -1 and neither feels nor exerts a
+ * contact force; this pass sets fl_k = -2, from which on the child collides like any other berg, for every live child that has
+ * no other berg -- its parent and its siblings count, whatever their fl_k -- within contact range: closer than
+ * max(R1 + R2, contact_distance) with contact_cells_lon = contact_cells_lat = 1, than contact_distance otherwise, looked for in
+ * the cells i-contact_cells_lon .. i+contact_cells_lon by j-contact_cells_lat .. j+contact_cells_lat around the child's own,
+ * cut at isd+1 .. ied, jsd+1 .. jed.  Only fl_k of promoted rows changes.  Its place in a step driven phase by phase:
+ *   kid_zero_accumulators, [kid_interp_gridded_fields_to_bergs], kid_evolve_icebergs, kid_footloose_calving,
+ *   [kid_set_conglom_ids with contact_distance > 0 or contact_spring_coef /= spring_coef], [kid_interp_gridded_fields_to_bergs],
+ *   kid_adjust_fl_berg_interactivity, kid_thermodynamics, kid_create_gridded_icebergs_fields;
+ * kid_step_local and kid_run_step run this sequence themselves.  The cell tables of the contact searches are brought up to date
+ * first, so that rows appended since they were built (the children of this step) are candidates and partners.
+ * promoted: the number of children the call promoted (one 4-byte read and a stream synchronisation); NULL: nothing is read
+ * back and the call only enqueues.  Nothing happens (and *promoted = 0) unless footloose and interactive_icebergs_on are both on.
+ * KID_EINVAL while halo rows are resident (kid_pack_halo_bergs_pair above). */
+int kid_adjust_fl_berg_interactivity(kid_handle *h, int64_t *promoted);
 int kid_thermodynamics(kid_handle *h);
 int kid_create_gridded_icebergs_fields(kid_handle *h);
 
