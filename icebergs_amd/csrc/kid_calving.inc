@@ -387,7 +387,19 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   const CalveCtx cx{d_reserve, h->d_iceberg_counter, (long long)h->n, (long long)h->capacity, id_iNg(d), id_ij0(d), h->d_calv_list};
   a.part = h->d_calv_part + (size_t)nb_acc * CALV_PART_ACC;
   hipLaunchKernelGGL(calve_count_kernel, dim3((unsigned)((n0 + 1023) / 1024)), dim3(1024), 0, h->stream, dev_grid(h), h->d_params, a, cx);
-  hipLaunchKernelGGL(calve_emit_kernel, dim3(nb_calve), dim3(256), 0, h->stream, dev_grid(h), h->d_params, h->bp, a, cx);
+  CalveCtx cx_emit = cx;
+  if (h->auto_growth != 0.) {
+    // auto-reserve: the count pass has reserved every row the call appends; read that word (the one extra synchronisation of
+    // the mode), grow, and hand the new capacity and field pointers to the emit pass
+    unsigned long long word = 0ull;
+    KID_HIP(h, hipGetLastError());
+    KID_HIP(h, hipMemcpyAsync(&word, d_reserve, sizeof(word), hipMemcpyDeviceToHost, h->stream));
+    KID_HIP(h, hipStreamSynchronize(h->stream));
+    const int rc_a = auto_reserve(h, h->n + (int64_t)(word & 0xffffffffull), "kid_calving");
+    if (rc_a) return rc_a;   // (the buckets keep their ice: nothing was emitted)
+    cx_emit.capacity = (long long)h->capacity;
+  }
+  hipLaunchKernelGGL(calve_emit_kernel, dim3(nb_calve), dim3(256), 0, h->stream, dev_grid(h), h->d_params, h->bp, a, cx_emit);
   {
     CalvFinish f{a.part, nb_calve, CALV_PART_CALVE, a.scal, {}, d_reserve};
     f.dst[0] = KID_CS_NET_CALVING_TO_BERGS; f.dst[1] = KID_CS_NET_HEAT_TO_BERGS; f.dst[2] = KID_CS_ERROR_COUNT; f.dst[3] = KID_CS_NBERGS_CALVED;

@@ -49,6 +49,8 @@ struct kid_handle {
   int ni = 0, nj = 0;
   size_t ncell = 0;
   int64_t capacity = 0, n = 0;
+  // kid_set_auto_reserve (kid_reserve.inc): auto_growth = 0 is off; the entry points that append rows grow the handle by this rule
+  double auto_growth = 0.; int64_t auto_min_free = 0, auto_max_capacity = 0;
   // device memory
   double *d_static[KID_NGRID_STATIC] = {}, *d_forcing[KID_NFORCING] = {};
   VelRec *d_vel = nullptr; TrcRec *d_trc = nullptr; GeoRec *d_geo = nullptr; double *d_hotok = nullptr; double *d_latref = nullptr;
@@ -174,4 +176,5 @@ static bool plain_namelist(const kid_handle *h), lanes_eligible(const kid_handle
 static int repro_refuse(kid_handle *h);                                                  // kid_repro.inc
 static int mts_check_timeout(kid_handle *h), mts_fold_scalars(kid_handle *h);            // kid_mts_host.inc
 static int halo_bergs_supported(kid_handle *h, const char *what);                                                                           // kid_halo_bergs.inc
+static int auto_reserve(kid_handle *h, int64_t need, const char *what);                  // kid_reserve.inc
 }

@@ -32,6 +32,7 @@
 #include "kid_berg_kernel.hpp"
 #include "kid_rows_plan.hpp"
 #include "kid_fl_contact.hpp"
+#include "kid_reserve_plan.hpp"
 
 using namespace kid;
 
@@ -666,6 +667,7 @@ extern "C" {
 
 int kid_upload_bergs(kid_handle *h, const kid_berg_soa *host) {
   if (!h || !host || host->n < 0) return KID_EINVAL;
+  if (host->n > h->capacity) { const int rc = auto_reserve(h, host->n, "kid_upload_bergs"); if (rc) return rc; }
   if (host->n > h->capacity) { h->err = "more bergs than capacity"; return KID_ECAPACITY; }
   { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }
   const size_t n = (size_t)host->n;
@@ -800,6 +802,9 @@ int kid_footloose_calving(kid_handle *h) {
   rc = refresh_tables(h);
   if (rc) return rc;
   h->flags.has_fl = 1;
+  // auto-reserve: min_free rows behind the parents before the launch (no retry afterwards: the parents' bits are spent by then)
+  rc = auto_reserve(h, h->n + h->auto_min_free, "kid_footloose_calving");
+  if (rc) return rc;
   KID_HIP(h, hipMemsetAsync(h->d_fl_cursor, 0, sizeof(int), h->stream));
   const unsigned fl_step_now = h->fl_step;
   FlChildCtx cx{h->d_fl_cursor, h->d_iceberg_counter, (long long)h->n, (long long)h->capacity, h->gd.iec - h->gd.isc + 1, h->fl_step++};
@@ -861,6 +866,7 @@ static int launch_gather(kid_handle *h) {
 #include "kid_bond_init.inc"
 #include "kid_budget.inc"
 #include "kid_launch.inc"
+#include "kid_reserve.inc"
 extern "C" {
 
 int kid_get_accumulators(kid_handle *h, double *acc, double *out, double *scalars) {

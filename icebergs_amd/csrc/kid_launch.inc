@@ -333,6 +333,7 @@ static int step_interactive(kid_handle *h) {   // single-time-step scheme with i
 // the SoA instead of three (SURVEY 8d: 320 B per berg-step instead of 530).  The children it appends are new rows; they
 // owe this step's thermodynamics and spreading, which a second, short launch over those rows delivers.
 static int step_footloose_fused(kid_handle *h) {
+  { const int rc_a = auto_reserve(h, h->n + h->auto_min_free, "kid_step_local"); if (rc_a) return rc_a; }   // (one host compare while the mode is off or room is left)
   h->flags.has_fl = 1;
   KID_HIP(h, hipMemsetAsync(h->d_fl_cursor, 0, sizeof(int), h->stream));
   const long long n_old = h->n;

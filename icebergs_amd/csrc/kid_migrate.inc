@@ -235,6 +235,7 @@ static int unpack_core(kid_handle *h, const double *buf_a, int64_t m_a, const do
     const int rc = kid_compact_bergs(h);
     if (rc) return rc;
   }
+  if (h->n + m > h->capacity) { const int rc = auto_reserve(h, h->n + m, "kid_unpack_immigrants"); if (rc) return rc; }   // the remainder: grow
   if (h->n + m > h->capacity) { h->err = "kid_unpack_immigrants: out of capacity: create the handle with room for arrivals"; return KID_ECAPACITY; }
   const size_t mm = (size_t)m;
   { const int rc = mig_stage(h, m); if (rc) return rc; }

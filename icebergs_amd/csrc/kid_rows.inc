@@ -177,7 +177,13 @@ static int rows_appended(kid_handle *h, int64_t m, const double *records, const 
     h->uploaded_nonzero[KID_B_UVEL_OLD] |= h->uploaded_nonzero[KID_B_UVEL]; h->uploaded_nonzero[KID_B_VVEL_OLD] |= h->uploaded_nonzero[KID_B_VVEL];
     h->uploaded_nonzero[KID_B_LON_OLD] |= h->uploaded_nonzero[KID_B_LON]; h->uploaded_nonzero[KID_B_LAT_OLD] |= h->uploaded_nonzero[KID_B_LAT];
   }
-  if (m > h->capacity - h->n) { h->n = h->capacity; h->err = full; return KID_ECAPACITY; }
+  if (m > h->capacity - h->n) {
+    h->err = full;
+    // auto-reserve made min_free rows of room before the launch and the launch wanted more: say how many
+    if (h->auto_growth != 0.) h->err += " (the launch tried to append " + std::to_string(m) + " rows, " + std::to_string(h->capacity - h->n) + " were free: raise min_free of kid_set_auto_reserve)";
+    h->n = h->capacity;
+    return KID_ECAPACITY;
+  }
   h->n += m;
   return KID_OK;
 }

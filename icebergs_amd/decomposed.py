@@ -91,6 +91,17 @@ class HipTile:
     def unpack_pair(self, from_lo, from_hi):
         self.ib.unpack_immigrants_pair(from_lo, from_hi)
 
+    # growable capacity, per tile: a TileExchange run opts in for the tiles that need it
+    @property
+    def capacity(self):
+        return self.ib.capacity
+
+    def reserve(self, rows):
+        self.ib.reserve(rows)
+
+    def set_auto_reserve(self, min_free, growth=1.5, max_capacity=0):
+        self.ib.set_auto_reserve(min_free, growth, max_capacity)
+
 
 class TileExchange:
     """ranks laid out as an ntx x nty array of tiles, rank = ty * ntx + tx (x fastest, like the reference's domain layout);

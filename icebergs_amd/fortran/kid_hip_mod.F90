@@ -43,6 +43,7 @@ module kid_hip_mod
   public :: kid_initialize_bonds, kid_count_bonds
   public :: kid_budget_out, kid_budget, kid_stock, kid_incr_mass
   public :: kid_calculate_mass_on_ocean, kid_halo_plane_count, kid_halo_buffer_count, kid_pack_halo_pair, kid_unpack_halo_pair
+  public :: kid_capacity, kid_reserve, kid_set_auto_reserve
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -231,6 +232,23 @@ module kid_hip_mod
       import :: c_int, c_ptr
       type(c_ptr), value :: h
       integer(c_int), value :: steps
+    end function
+    ! growable capacity: the rows a handle has room for, more of them, and growth ahead of the calls that append rows
+    integer(c_int) function kid_capacity(h, rows) bind(C, name='kid_capacity')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), intent(out) :: rows
+    end function
+    integer(c_int) function kid_reserve(h, rows) bind(C, name='kid_reserve')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), value :: rows
+    end function
+    integer(c_int) function kid_set_auto_reserve(h, min_free, growth, max_capacity) bind(C, name='kid_set_auto_reserve')
+      import :: c_int, c_ptr, c_int64_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int64_t), value :: min_free, max_capacity
+      real(c_double), value :: growth
     end function
     type(c_ptr) function kid_version() bind(C, name='kid_version')   ! a NUL-terminated string: the library and its build switches
       import :: c_ptr

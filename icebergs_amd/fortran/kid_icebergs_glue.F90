@@ -29,7 +29,7 @@ module kid_icebergs_glue
   public :: iceberg, bond, linked_list, kid_glue, inorder, insert_berg_into_list, kid_glue_init, kid_glue_set_calving, kid_glue_add_berg, kid_glue_count, &
             kid_glue_flatten, kid_glue_unflatten, kid_glue_clear_lists, kid_glue_end, kid_icebergs_run, kid_icebergs_init, kid_read_icebergs_nml, &
             kid_icebergs_init_bonds, kid_icebergs_run_local, kid_icebergs_run_finish, kid_exchange_sum, row_to_node, node_to_row, form_a_bond, kid_glue_find_berg, KID_CYCLIC_GLOBAL_DOMAIN, &
-            kid_icebergs_stock_pe, kid_icebergs_incr_mass
+            kid_icebergs_stock_pe, kid_icebergs_incr_mass, kid_glue_reserve
   !> FMS's mpp_domains flag for a zonally periodic global domain (mpp_parameter_mod), as DRV:44 passes it in dom_x_flags
   integer, parameter :: KID_CYCLIC_GLOBAL_DOMAIN = 2
 
@@ -75,7 +75,8 @@ module kid_icebergs_glue
     type(linked_list), allocatable :: list(:,:)               ! (isd:ied, jsd:jed), FW:423
     real(c_double), allocatable :: area(:,:)                   ! grd%area on the data domain (the coupler return needs it, IB:5655)
     real(c_double), allocatable :: static(:,:,:)               ! the grid kid_icebergs_init built, KID_G_* planes on the data domain
-    integer(c_int64_t) :: capacity = 0
+    integer(c_int64_t) :: capacity = 0     ! rows of the staging arrays below (kid_glue_reserve grows them, and the handle)
+    real(c_double) :: auto_reserve_growth = 0.   ! > 0: the handle grows ahead of appends (kid_set_auto_reserve) and the staging follows
     logical :: calving_on = .false.        ! the calving source runs on the device too (kid_glue_set_calving)
     logical :: tau_is_velocity = .false.   ! bergs%tau_is_velocity (FW:727): tauxa / tauya are winds, not stresses
     logical :: passive_mode = .false.      ! bergs%passive_mode (FW:728): nothing is returned to the coupler
@@ -184,11 +185,14 @@ contains
   !!   namelist (FW:879) -> derived switches (FW:1243-1326, 1433-1531) -> data-domain grid (FW:921-1147) -> kid_create,
   !!   kid_set_static_grid, the class tables of the calving source (FW:1534-1551), the trajectory switches.
   !! `capacity` (not in the reference: its lists grow on the heap) sizes the device arrays; nml_file defaults to 'input.nml'.
+  !! auto_reserve_growth / auto_reserve_min_free (either one switches the mode on; growth defaults to 1.5, min_free to 0) give
+  !! the lists' one convenience back: the handle grows before calving, footloose children or a larger upload would overflow it
+  !! (kid_set_auto_reserve), and the staging arrays follow.  With both absent a population that outgrows `capacity` stops the run.
   !! Restart reading stays with the caller (kid_read_restart, or kid_glue_add_berg + form_a_bond for a population of its own);
   !! call kid_icebergs_init_bonds after the population is in the lists for the bonded / DEM tail of icebergs_init (IB:141-176).
   subroutine kid_icebergs_init(bergs, gni, gnj, layout, io_layout, axes, dom_x_flags, dom_y_flags, dt, year, yearday, &
                                ice_lon, ice_lat, ice_wet, ice_dx, ice_dy, ice_area, cos_rot, sin_rot, ocean_depth, maskmap, fractional_area, &
-                               capacity, nml_file, device)
+                               capacity, nml_file, device, auto_reserve_growth, auto_reserve_min_free)
     type(kid_glue), intent(inout), target :: bergs
     integer, intent(in) :: gni, gnj, layout(2), io_layout(2), axes(2), dom_x_flags, dom_y_flags
     real(c_double), intent(in) :: dt
@@ -200,6 +204,8 @@ contains
     integer(c_int64_t), intent(in), optional :: capacity
     character(len=*), intent(in), optional :: nml_file
     integer, intent(in), optional :: device
+    real(c_double), intent(in), optional :: auto_reserve_growth
+    integer(c_int64_t), intent(in), optional :: auto_reserve_min_free
     real(c_double), parameter :: fms_pi = 3.14159265358979323846_c_double, fms_omega = 7.292e-5_c_double, fms_hlf = 3.34e5_c_double, &
                                  fms_radius = 6371.0e3_c_double   ! constants_mod (FW:6): pi, omega, HLF, radius
     real(c_double), parameter :: big_number = 1.0e15_c_double
@@ -212,7 +218,7 @@ contains
     type(c_ptr) :: pst(KID_NGRID_STATIC)
     real(c_double) :: lon_mod, mts_fast_dt, dx_dlon, dy_dlat, ddx, ddy, pi_180, total_s, total_n, rem_s, rem_n
     integer :: isc, iec, jsc, jec, isd, ied, jsd, jed, ni, nj, i, j, k, maxk, f, last_s, last_n, dev
-    integer(c_int64_t) :: cap
+    integer(c_int64_t) :: cap, ar_min_free
     logical :: cyclic_x, cyclic_y
 
     if (layout(1) * layout(2) /= 1) error stop 'kid_icebergs_init: one handle owns one rectangle of cells -- call it per PE with that PE''s extents (INTEGRATION.md section 6)'
@@ -449,6 +455,11 @@ contains
     call kid_check(kid_create(gd, par, cap, int(dev, c_int), bergs%h), bergs%h, 'kid_create')
     do f = 1, KID_NGRID_STATIC ; pst(f) = c_loc(st(isd, jsd, f)) ; enddo
     call kid_check(kid_set_static_grid(bergs%h, pst), bergs%h, 'kid_set_static_grid')
+    if (present(auto_reserve_growth) .or. present(auto_reserve_min_free)) then
+      bergs%auto_reserve_growth = 1.5_c_double ; if (present(auto_reserve_growth)) bergs%auto_reserve_growth = auto_reserve_growth
+      ar_min_free = 0 ; if (present(auto_reserve_min_free)) ar_min_free = auto_reserve_min_free
+      call kid_check(kid_set_auto_reserve(bergs%h, ar_min_free, bergs%auto_reserve_growth, 0_c_int64_t), bergs%h, 'kid_set_auto_reserve')
+    endif
     allocate(bergs%list(isd:ied, jsd:jed))
     allocate(bergs%area(ni, nj)) ; bergs%area = area
     allocate(bergs%static(ni, nj, KID_NGRID_STATIC)) ; bergs%static = st
@@ -660,6 +671,41 @@ contains
     enddo ; enddo
   end subroutine kid_glue_clear_lists
 
+  !> room for `rows` bergs, on the device (kid_reserve: never shrinks, rows keep their numbers) and in the staging arrays,
+  !! whose contents are kept
+  subroutine kid_glue_reserve(g, rows)
+    type(kid_glue), intent(inout) :: g
+    integer(c_int64_t), intent(in) :: rows
+    call kid_check(kid_reserve(g%h, rows), g%h, 'kid_reserve')
+    call grow_staging(g, rows)
+  end subroutine kid_glue_reserve
+
+  !> the staging arrays alone: f64, i32, ids and, where they exist, the bond arrays, reallocated with their contents
+  subroutine grow_staging(g, rows)
+    type(kid_glue), intent(inout) :: g
+    integer(c_int64_t), intent(in) :: rows
+    real(c_double), allocatable :: f64(:,:), bf64(:,:,:)
+    integer(c_int32_t), allocatable :: i32(:,:), bcount(:), bbroken(:,:)
+    integer(c_int64_t), allocatable :: ids(:), bother(:,:)
+    integer(c_int64_t) :: old
+    old = g%capacity
+    if (rows <= old) return
+    allocate(f64(rows, KID_NB_F64), i32(rows, KID_NB_I32), ids(rows))
+    f64 = 0. ; i32 = 0 ; ids = 0
+    if (allocated(g%f64)) then
+      f64(1:old, :) = g%f64(1:old, :) ; i32(1:old, :) = g%i32(1:old, :) ; ids(1:old) = g%ids(1:old)
+    endif
+    call move_alloc(f64, g%f64) ; call move_alloc(i32, g%i32) ; call move_alloc(ids, g%ids)
+    if (allocated(g%bcount)) then
+      allocate(bcount(rows), bbroken(rows, size(g%bbroken, 2)), bother(rows, size(g%bother, 2)), bf64(rows, size(g%bf64, 2), size(g%bf64, 3)))
+      bcount = 0 ; bbroken = 0 ; bother = 0 ; bf64 = 0.
+      bcount(1:old) = g%bcount(1:old) ; bbroken(1:old, :) = g%bbroken(1:old, :) ; bother(1:old, :) = g%bother(1:old, :)
+      bf64(1:old, :, :) = g%bf64(1:old, :, :)
+      call move_alloc(bcount, g%bcount) ; call move_alloc(bbroken, g%bbroken) ; call move_alloc(bother, g%bother) ; call move_alloc(bf64, g%bf64)
+    endif
+    g%capacity = rows
+  end subroutine grow_staging
+
   !> lists -> structure of arrays in the reference's traversal order (cells j outer / i inner, IB:7106; list order inside a
   !! cell), and upload.  Row k of every column is the k-th berg the reference's loops would visit.
   subroutine kid_glue_flatten(g)
@@ -669,7 +715,10 @@ contains
     integer :: grdi, grdj, k
     integer(c_int64_t) :: n
     n = kid_glue_count(g)
-    if (n > g%capacity) error stop 'kid_glue_flatten: more bergs than the handle has rows for'
+    if (n > g%capacity) then   ! auto-reserve: the staging grows here, the handle inside kid_upload_bergs
+      if (g%auto_reserve_growth <= 0.) error stop 'kid_glue_flatten: more bergs than the handle has rows for'
+      call grow_staging(g, n)
+    endif
     g%f64 = 0. ; g%i32 = 0 ; g%ids = 0
     n = 0
     do grdj = g%gd%jsc, g%gd%jec ; do grdi = g%gd%isc, g%gd%iec
@@ -758,7 +807,7 @@ contains
     logical :: rev
     rev = .false. ; if (present(keep_list_order)) rev = keep_list_order
     call kid_check(kid_num_bergs(g%h, n_slots, n_alive), g%h, 'kid_num_bergs')
-    if (n_slots > g%capacity) error stop 'kid_glue_unflatten: the population outgrew the staging arrays'
+    if (n_slots > g%capacity) call grow_staging(g, n_slots)   ! the handle has grown (kid_reserve, auto-reserve): the staging follows
     soa%n = n_slots
     do q = 1, KID_NB_F64 ; soa%f64(q) = c_loc(g%f64(1,q)) ; enddo
     do q = 1, KID_NB_I32 ; soa%i32(q) = c_loc(g%i32(1,q)) ; enddo

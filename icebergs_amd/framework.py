@@ -542,6 +542,23 @@ class Icebergs:
     def compact(self):
         self._check(self.lib.kid_compact_bergs(self.h), "kid_compact_bergs")
 
+    # ---- growable capacity (include/kid.h): host buffers are sized from num_bergs(), never from the capacity of __init__ ----
+    @property
+    def capacity(self):
+        """the handle's current row capacity: what __init__ was given, or what reserve / auto-reserve have made of it since"""
+        n = C.c_int64()
+        self._check(self.lib.kid_capacity(self.h, C.byref(n)), "kid_capacity")
+        return n.value
+
+    def reserve(self, rows):
+        """make the capacity at least `rows` (never shrinks); rows keep their numbers, so bonds and halo rows survive"""
+        self._check(self.lib.kid_reserve(self.h, int(rows)), "kid_reserve")
+
+    def set_auto_reserve(self, min_free, growth=1.5, max_capacity=0):
+        """the calls that append rows grow the handle before they write: to max(need, ceil(capacity * growth)), at most
+        max_capacity (0: 2^29); a footloose launch is given `min_free` free rows.  growth=0 switches it off (the default)."""
+        self._check(self.lib.kid_set_auto_reserve(self.h, int(min_free), float(growth), int(max_capacity)), "kid_set_auto_reserve")
+
     # ---- icebergs_run, the hot-path part (IB:5423-5512) ----
     def run(self, nsteps=1):
         """Fused path: per step one per-berg launch (evolve + thermodynamics + spreading) and one gather."""

@@ -101,6 +101,33 @@ int kid_compact_bergs(kid_handle *h);
 int kid_move_berg_between_cells(kid_handle *h);
 int kid_set_resort_interval(kid_handle *h, int steps);
 
+/* ---- growable capacity: the one convenience of the reference's linked lists, which grow on the heap ---- */
+/* The handle's current row capacity: what kid_create was given, or what kid_reserve / auto-reserve have made of it since. */
+int kid_capacity(kid_handle *h, int64_t *rows);
+/* Makes the capacity at least `rows`.  rows <= the current capacity changes nothing and returns KID_OK (a handle never
+ * shrinks); rows > 2^29, the limit of kid_create, is KID_EINVAL.  Rows keep their numbers, so the call is legal with bond
+ * tables, with halo rows resident and in a decomposed run with bergs waiting to be packed; it joins the side stream, runs a
+ * pending re-binning and leaves the slow-lane schedule.  Afterwards every result is what a handle created at the new
+ * capacity and brought to the same state would give.  Every block that holds state is moved on its own (allocate, copy the
+ * first n rows, swap, free), so the most held at any moment is the new total plus one old block; scratch is reallocated, or
+ * freed and allocated again by whoever needs it next.  If the device runs out of memory the call returns KID_EHIP with the
+ * runtime's message and the handle is valid at the old capacity.  Not a step-path call: it synchronises the stream once per
+ * block. */
+int kid_reserve(kid_handle *h, int64_t rows);
+/* Auto-reserve, off by default: the entry points that append rows make room before they write.  growth = 0 switches it off;
+ * otherwise growth >= 1 and min_free >= 0, and max_capacity = 0 means 2^29 (anything else: KID_EINVAL).  A call that is
+ * about to hold `need` rows, more than the capacity, grows the handle to min(max_capacity, max(need, ceil(capacity * growth)));
+ * need > max_capacity is KID_ECAPACITY before anything is written, and kid_last_error names both numbers.
+ *   count known first: kid_upload_bergs (host->n), kid_unpack_immigrants[_pair] (what is left over after the compaction they
+ *     already try) and kid_calving (between its count pass and its emit pass: one more stream synchronisation, in this mode
+ *     only) cannot overflow any more;
+ *   children made inside a per-berg launch (kid_footloose_calving, kid_step_local / kid_run_step with footloose, at every
+ *     step): capacity - n >= min_free is ensured before the launch.  A launch that makes more children than that is still
+ *     KID_ECAPACITY -- no retry, the parents' bits are spent -- and the message gives the number of rows it tried to append:
+ *     choose min_free from the largest per-step append the run has seen.
+ * With the mode off every call behaves and reports exactly as before. */
+int kid_set_auto_reserve(kid_handle *h, int64_t min_free, double growth, int64_t max_capacity);
+
 /* berg%uo..od (the last interpolated environment).  With old_interp_flds_order accel re-interpolates (IB:2035) and the
  * stored copy is read only by trajectory records (FW:5422) and bergs_chksum (FW:7040): a run with ignore_traj=T may
  * switch it off (on = 0) and save 13 stores per berg per step.  With .not.old_interp_flds_order the stored environment is
