@@ -8,6 +8,8 @@
 // isc-w .. iec+w, which carry the corners the first pass has filled (the two hops of mpp_update_domains).
 // The work is latency, not bytes (a 1440 x 1080 tile sends 36 x 1080 doubles east): one launch per call, one thread per
 // element, plain loads and stores.
+// A tile of the top row of a tripolar grid takes its mirror partner's north strip over the fold instead of a north
+// neighbour's south strip: kid_unpack_halo_fold / kid_fold_halo_self (IB:6110-6122), further down.
 namespace {
 // one strip per side (0: hi = east / north, 1: lo = west / south): nrow x ncol cells of every plane, the first of them at
 // (col0[side], row0[side]) counted from the corner of the data domain; buf[side] == nullptr: no neighbour there
@@ -24,6 +26,24 @@ __global__ void __launch_bounds__(256) halo_strips_kernel(double *__restrict__ p
   const int c = e % s.ncol, r = (e / s.ncol) % s.nrow, pl = e / (s.ncol * s.nrow);
   double *cell = planes + (size_t)pl * ncell + (size_t)(s.row0[side] + r) * s.ni + (size_t)(s.col0[side] + c);
   if (PACK) buf[e] = *cell; else *cell = buf[e];
+}
+// The tripolar north fold (DESIGN 7.5): a tile of the top row takes the strip its mirror partner packed for the north (rows
+// jec-w+1 .. jec, columns isc-w .. iec+w) into its own rows jec+1 .. jec+w turned by 180 degrees -- FMS's
+// halo(i, nj+k) = field(ni+1-i, nj+1-k) for a centred scalar -- and with the nine slots of every group mirrored through the
+// centre (1<->9, 2<->8, 3<->7, 4<->6 of IB:6117-6120; swap == 0: old_bug_rotated_weights, the slot stays).
+// row_src: the strip's first row in the planes (SELF only), row_top: the row strip row 0 lands in (jec + w).
+struct FoldStrip { int np, w, ncol, ni, col0, row_src, row_top, swap; const double *buf; };
+// SELF: the partner is the handle itself (it owns the whole zonal width), planes to planes.  What a thread reads (rows <= jec)
+// and what any thread writes (rows > jec) are disjoint, so the one launch needs no ordering between its threads.
+template <bool SELF>
+__global__ void __launch_bounds__(256) halo_fold_kernel(double *__restrict__ planes, const size_t ncell, const FoldStrip s) {
+  const int per = s.np * s.w * s.ncol;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= per) return;
+  const int c = e % s.ncol, r = (e / s.ncol) % s.w, pl = e / (s.ncol * s.w);
+  const int to = s.swap ? pl - pl % 9 + (8 - pl % 9) : pl;
+  const double v = SELF ? planes[(size_t)pl * ncell + (size_t)(s.row_src + r) * s.ni + (size_t)(s.col0 + c)] : s.buf[e];
+  planes[(size_t)to * ncell + (size_t)(s.row_top - r) * s.ni + (size_t)(s.col0 + s.ncol - 1 - c)] = v;
 }
 }  // namespace
 
@@ -65,6 +85,22 @@ static int halo_launch(kid_handle *h, const HaloStrips &s) {
   const long long total = 2ll * s.np * s.nrow * s.ncol;
   hipLaunchKernelGGL(halo_strips_kernel<PACK>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
                      h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, h->ncell, s);
+  KID_HIP(h, hipGetLastError());
+  return KID_OK;
+}
+
+// the fold strip of one call: the north strip of kid_pack_halo_pair(axis 1), mirrored into the rows above jec
+static bool fold_strip(const kid_handle *h, int w, FoldStrip &f) {
+  HaloStrips s;
+  if (!halo_strips(h, 1, w, true, s)) return false;
+  f.np = s.np; f.w = w; f.ncol = s.ncol; f.ni = s.ni; f.col0 = s.col0[0]; f.row_src = s.row0[0]; f.row_top = s.row0[0] + 2 * w - 1; f.buf = nullptr;
+  return true;
+}
+template <bool SELF>
+static int fold_launch(kid_handle *h, const FoldStrip &f) {
+  const long long total = (long long)f.np * f.w * f.ncol;
+  hipLaunchKernelGGL(halo_fold_kernel<SELF>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
+                     h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, h->ncell, f);
   KID_HIP(h, hipGetLastError());
   return KID_OK;
 }
@@ -126,6 +162,35 @@ int kid_unpack_halo_pair(kid_handle *h, int32_t axis, int32_t width, const doubl
   if (from_lo) std::memcpy(h->halo_buf + per, from_lo, (size_t)per * sizeof(double));
   s.buf[0] = from_hi ? h->halo_buf : nullptr; s.buf[1] = from_lo ? h->halo_buf + per : nullptr;
   return halo_launch<false>(h, s);   // no wait: the caller's buffers are free already and the stream orders the gather behind it
+}
+
+int kid_unpack_halo_fold(kid_handle *h, int32_t width, const double *from_fold, int32_t swap_slots, int32_t on_device) {
+  if (!h) return KID_EINVAL;
+  FoldStrip f;
+  if (!fold_strip(h, width, f)) return halo_refuse(h, "kid_unpack_halo_fold");
+  if (!from_fold) { h->err = "kid_unpack_halo_fold: from_fold is NULL (a fold tile always has a partner)"; return KID_EINVAL; }
+  { const int rc_h = halo_rows_refuse(h, "kid_unpack_halo_fold"); if (rc_h) return rc_h; }
+  KID_HIP(h, hipSetDevice(h->device));
+  { const int rc = join_side(h); if (rc) return rc; }
+  f.swap = swap_slots ? 1 : 0;
+  if (on_device) { f.buf = from_fold; return fold_launch<false>(h, f); }
+  const long long per = (long long)f.np * f.w * f.ncol;
+  { const int rc = halo_stage(h, 2 * per); if (rc) return rc; }   // (the size the north/south pair of the same width asks for: no regrowth between the two)
+  KID_HIP(h, hipStreamSynchronize(h->stream));   // an earlier unpack launch may still be reading the staging buffer
+  std::memcpy(h->halo_buf, from_fold, (size_t)per * sizeof(double));
+  f.buf = h->halo_buf;
+  return fold_launch<false>(h, f);   // no wait, as kid_unpack_halo_pair
+}
+
+int kid_fold_halo_self(kid_handle *h, int32_t width, int32_t swap_slots) {
+  if (!h) return KID_EINVAL;
+  FoldStrip f;
+  if (!fold_strip(h, width, f)) return halo_refuse(h, "kid_fold_halo_self");
+  { const int rc_h = halo_rows_refuse(h, "kid_fold_halo_self"); if (rc_h) return rc_h; }
+  KID_HIP(h, hipSetDevice(h->device));
+  { const int rc = join_side(h); if (rc) return rc; }
+  f.swap = swap_slots ? 1 : 0;
+  return fold_launch<true>(h, f);
 }
 
 }  // extern "C"

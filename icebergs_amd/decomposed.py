@@ -23,11 +23,18 @@ The third exchange is for interacting bergs: `TileExchange.update_halo_bergs` br
 shared edges (update_halo_icebergs, FW:1800-2131) so that contact forces cross tile edges, and `TileExchange.step_interactive`
 is the step that uses it.  The tile offers `pack_halo_bergs_pair(axis, width, sides)` -> (records for the east/north neighbour,
 for the west/south one) and `set_conglom_ids()`; the records come in through `unpack_pair`.
+
+A tripolar grid closes its north edge on itself (FOLD_NORTH_EDGE): `TileExchange(..., fold_north=True)` gives a tile of the top
+row its mirror tile as the partner beyond the fold (grd%pe_N of FW:3138-3195).  The partner's north strip of the on-ocean planes
+arrives turned by 180 degrees (`unpack_halo_fold`, or `fold_halo_self` where the tile is its own partner; IB:6110-6122), and a
+berg that walks north over the fold arrives on the partner with its cell index mirrored.  For this the tile also offers
+`comp_domain()` -> (isc, iec, jsc, jec), `unpack_halo_fold(from_fold, width, swap_slots)` and `fold_halo_self(width, swap_slots)`.
 """
 import numpy as np
 import torch
 
 WIDTH = 34  # buffer_width without bonds, FW:21
+W_INE, W_JNE = 23, 24  # reals 24 and 25 of the wire record (pack_berg_into_buffer2, FW:3291-3292), 0-based
 
 
 class HipTile:
@@ -79,6 +86,16 @@ class HipTile:
     def unpack_halo_pair(self, axis, from_lo, from_hi, width=1):
         self.ib.unpack_halo_pair(axis, from_lo, from_hi, width)
 
+    def unpack_halo_fold(self, from_fold, width=1, swap_slots=True):
+        self.ib.unpack_halo_fold(from_fold, width, swap_slots)
+
+    def fold_halo_self(self, width=1, swap_slots=True):
+        self.ib.fold_halo_self(width, swap_slots)
+
+    def comp_domain(self):
+        d = self.ib.grid["desc"]
+        return d.isc, d.iec, d.jsc, d.jec
+
     def pack_pair(self, axis):
         return self.ib.pack_emigrants_pair(axis)
 
@@ -106,16 +123,25 @@ class HipTile:
 class TileExchange:
     """ranks laid out as an ntx x nty array of tiles, rank = ty * ntx + tx (x fastest, like the reference's domain layout);
     a tile on the edge of the box has no neighbour there (NULL_PE: its leavers are packed and dropped, FW:3050) unless
-    cyclic_x closes the zonal direction"""
+    cyclic_x closes the zonal direction or fold_north the north edge: the partner of tile (tx, nty-1) beyond the fold is
+    (ntx-1-tx, nty-1), the tile itself for ntx == 1 and for the middle tile of an odd ntx.  fold_north needs tiles of one width
+    (tile_widths: the computational columns of every tile column, where the caller knows them; they must all be equal), since
+    only then is a tile's mirror image one tile"""
 
-    def __init__(self, ntx, nty, dist, rank=None, cyclic_x=False, device="cpu"):
+    def __init__(self, ntx, nty, dist, rank=None, cyclic_x=False, device="cpu", fold_north=False, tile_widths=None):
         self.ntx, self.nty, self.dist, self.device = int(ntx), int(nty), dist, device
         self.rank = dist.get_rank() if rank is None else int(rank)
         assert dist.get_world_size() == self.ntx * self.nty, "one rank per tile"
         self.tx, self.ty = self.rank % self.ntx, self.rank // self.ntx
         self.cyclic_x = bool(cyclic_x)
+        self.fold_north = bool(fold_north)
+        if self.fold_north and tile_widths is not None:
+            assert len(tile_widths) == self.ntx and len(set(int(w) for w in tile_widths)) == 1, "fold_north needs tiles that are uniform in x"
+        self._fold_nic = None if tile_widths is None else int(tile_widths[0])
+        self._fold_checked = False
         self.sent = 0          # records handed to neighbours so far
         self.received = 0
+        self.fold_records = np.empty((0, WIDTH))   # what the last exchange brought over the fold, cell indices already mirrored
 
     def neighbour(self, dx, dy):
         tx, ty = self.tx + dx, self.ty + dy
@@ -124,6 +150,29 @@ class TileExchange:
         if tx < 0 or tx >= self.ntx or ty < 0 or ty >= self.nty:
             return None
         return ty * self.ntx + tx
+
+    def fold_partner(self):
+        """the rank beyond the north fold (grd%pe_N of a top-row PE, FW:3138-3195); None for a tile below the top row or without fold_north"""
+        if not self.fold_north or self.ty != self.nty - 1:
+            return None
+        return self.ty * self.ntx + (self.ntx - 1 - self.tx)
+
+    def _fold_width_check(self, tile):
+        """uniform in x: this tile has the width the caller gave (tile_widths) and, asked of the partner once, the partner's"""
+        isc, iec, _, _ = tile.comp_domain()
+        nic = iec - isc + 1
+        assert self._fold_nic is None or nic == self._fold_nic, "fold_north needs tiles that are uniform in x"
+        self._fold_nic = nic
+        partner = self.fold_partner()
+        if self._fold_checked or partner == self.rank:
+            return
+        dist = self.dist
+        mine = torch.tensor([nic], dtype=torch.int64, device=self.device)
+        theirs = torch.zeros(1, dtype=torch.int64, device=self.device)
+        for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, mine, partner), dist.P2POp(dist.irecv, theirs, partner)]):
+            w.wait()
+        assert int(theirs.item()) == nic, "fold_north needs tiles that are uniform in x"
+        self._fold_checked = True
 
     def _swap(self, to_hi, hi, to_lo, lo):
         """send `to_hi` to rank `hi` and `to_lo` to rank `lo`; returns (from_lo, from_hi).  Counts first, then the records
@@ -190,10 +239,34 @@ class TileExchange:
 
     def exchange(self, tile):
         """send_bergs_to_other_pes for this rank's tile: call it between evolve_icebergs and thermodynamics (IB:5447)"""
+        partner = self.fold_partner()
+        self.fold_records = np.empty((0, WIDTH))
         for axis, (dx, dy) in enumerate(((1, 0), (0, 1))):
             to_hi, to_lo = tile.pack_pair(axis)
             hi, lo = self.neighbour(dx, dy), self.neighbour(-dx, -dy)
-            from_lo, from_hi = self._swap(to_hi, hi, to_lo, lo)
+            if axis == 1 and partner is not None:
+                # over the fold: what a top-row tile sends north goes to its mirror tile, and what that tile sent north arrives
+                # here from the north.  The partner sits in this tile's own row, so nothing else travels between the two in
+                # this pass, and the east/west pass has been waited for: the messages cannot be taken for one another
+                # (the reference gives them tags of their own, COMM_TAG_9/10, FW:3138-3195).
+                self._fold_width_check(tile)
+                if partner == self.rank:
+                    from_lo, _ = self._swap(to_hi[:0], None, to_lo, lo)
+                    from_hi = to_hi.copy()                    # straight back
+                    self.sent += len(to_hi)
+                    self.received += len(from_hi)
+                else:
+                    from_lo, from_hi = self._swap(to_hi, partner, to_lo, lo)
+                if len(from_hi):
+                    # the sender's cell (i, jec+k) beyond its north edge is this tile's cell (isc+iec-i, jec+1-k): with it the
+                    # first guess of the unpack holds (the reference scans for the cell and finds the same one)
+                    isc, iec, _, jec = tile.comp_domain()
+                    from_hi = np.array(from_hi, dtype=np.float64)
+                    from_hi[:, W_INE] = (isc + iec) - from_hi[:, W_INE]
+                    from_hi[:, W_JNE] = (2 * jec + 1) - from_hi[:, W_JNE]
+                    self.fold_records = from_hi
+            else:
+                from_lo, from_hi = self._swap(to_hi, hi, to_lo, lo)
             if len(from_lo) or len(from_hi):
                 tile.unpack_pair(from_lo, from_hi)            # from the west / south first, FW:3064, 3160
 
@@ -204,6 +277,8 @@ class TileExchange:
         two hops.  Counts, then records, as the migration.  width None: the grid's halo."""
         if self.cyclic_x:
             raise ValueError("TileExchange.update_halo_bergs does not cover cyclic_x (update_latlon, IB:5467; DESIGN 7.6, out of scope)")
+        if self.fold_north:
+            raise ValueError("TileExchange.update_halo_bergs does not cover fold_north (halo bergs across the fold; DESIGN 7.6, out of scope)")
         w = 0 if width is None else int(width)
         for axis, (dx, dy) in enumerate(((1, 0), (0, 1))):
             hi, lo = self.neighbour(dx, dy), self.neighbour(-dx, -dy)
@@ -219,6 +294,8 @@ class TileExchange:
         The halo bergs are taken right before the evolve (the reference takes them before the thermodynamics of the step
         before, IB:5462, so that a copy carries its owner's size of one melt earlier): a tile run sees what the undivided run sees."""
         p = tile.params
+        if self.fold_north:
+            raise ValueError("TileExchange.step_interactive does not cover fold_north (halo bergs across the fold; DESIGN 7.6, out of scope)")
         if not p.interactive_icebergs_on:
             raise ValueError("TileExchange.step_interactive needs interactive_icebergs_on; TileExchange.step covers the rest")
         for switch in ("find_melt_using_spread_mass", "mts", "iceberg_bonds_on", "footloose", "Runge_not_Verlet"):
@@ -269,9 +346,25 @@ class TileExchange:
     def update_halos(self, tile, width=1):
         """mpp_update_domains(var_on_ocean) of sum_up_spread_fields (IB:6106-6107) for this rank's tile: call it between
         calculate_mass_on_ocean and the gather.  East/west over the computational rows, then north/south over the columns
-        isc-width .. iec+width, which carry the corners the first pass has filled."""
+        isc-width .. iec+width, which carry the corners the first pass has filled.  With fold_north a top-row tile sends its north
+        strip to its mirror tile and takes that tile's strip turned by 180 degrees (IB:6110-6122), slots swapped unless
+        old_bug_rotated_weights."""
+        partner = self.fold_partner()
         for axis, (dx, dy) in enumerate(((1, 0), (0, 1))):
             hi, lo = self.neighbour(dx, dy), self.neighbour(-dx, -dy)
+            if axis == 1 and partner is not None:
+                self._fold_width_check(tile)
+                swap_slots = not tile.params.old_bug_rotated_weights
+                count = tile.halo_buffer_count(axis, width)
+                own = partner == self.rank
+                to_hi, to_lo = tile.pack_halo_pair(axis, width, (not own, lo is not None))
+                from_lo, from_fold = self._swap_halo(to_hi, None if own else partner, to_lo, lo, count)   # (ordering: see exchange)
+                if own:
+                    tile.fold_halo_self(width, swap_slots)
+                else:
+                    tile.unpack_halo_fold(from_fold, width, swap_slots)
+                tile.unpack_halo_pair(axis, from_lo, None, width)
+                continue
             if hi is None and lo is None:
                 continue
             count = tile.halo_buffer_count(axis, width)

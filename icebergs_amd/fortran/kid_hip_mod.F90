@@ -43,6 +43,7 @@ module kid_hip_mod
   public :: kid_initialize_bonds, kid_count_bonds
   public :: kid_budget_out, kid_budget, kid_stock, kid_incr_mass
   public :: kid_calculate_mass_on_ocean, kid_halo_plane_count, kid_halo_buffer_count, kid_pack_halo_pair, kid_unpack_halo_pair
+  public :: kid_unpack_halo_fold, kid_fold_halo_self
   public :: kid_capacity, kid_reserve, kid_set_auto_reserve
 
   interface
@@ -464,6 +465,18 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int32_t
       type(c_ptr), value :: h, from_lo, from_hi        ! what the west / south and the east / north neighbour packed
       integer(c_int32_t), value :: axis, width, on_device
+    end function
+    ! the tripolar north fold (include/kid.h): the strip the mirror rank packed as buf_hi of axis 1 into rows jec+1 .. jec+width,
+    ! turned by 180 degrees; swap_slots = 1 unless old_bug_rotated_weights (IB:6110-6122)
+    integer(c_int) function kid_unpack_halo_fold(h, width, from_fold, swap_slots, on_device) bind(C, name='kid_unpack_halo_fold')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h, from_fold
+      integer(c_int32_t), value :: width, swap_slots, on_device
+    end function
+    integer(c_int) function kid_fold_halo_self(h, width, swap_slots) bind(C, name='kid_fold_halo_self')   ! one rank owns the whole zonal width
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: width, swap_slots
     end function
     integer(c_int) function kid_evolve_icebergs_mts(h) bind(C, name='kid_evolve_icebergs_mts')   ! IB:5431
       import :: c_int, c_ptr

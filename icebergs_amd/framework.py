@@ -307,6 +307,24 @@ class Icebergs:
         if dev:
             self.sync()             # the tensors may be reused on return
 
+    # ---- the tripolar north fold (IB:6110-6122; include/kid.h has the mapping) ----
+    def unpack_halo_fold(self, from_fold, width=1, swap_slots=True):
+        """the strip the mirror partner packed for the north (its pack_halo_pair(1, width)[0]) into this handle's rows beyond the
+        fold, turned by 180 degrees; swap_slots: mirror the nine slots of every group as well (False: old_bug_rotated_weights).
+        from_fold: a numpy array or a torch tensor on the handle's device"""
+        count = self.halo_buffer_count(1, width)
+        assert from_fold is not None, "unpack_halo_fold: a fold tile always has a partner"
+        ptrs, dev = self._halo_buffers((from_fold,), count, "unpack_halo_fold")
+        if dev:
+            self._halo_order_in((from_fold,))
+        self._check(self.lib.kid_unpack_halo_fold(self.h, int(width), ptrs[0], int(bool(swap_slots)), int(dev)), "kid_unpack_halo_fold")
+        if dev:
+            self.sync()             # the tensor may be reused on return
+
+    def fold_halo_self(self, width=1, swap_slots=True):
+        """the same for a handle that owns the whole zonal width and so is its own partner: planes to planes, no buffer"""
+        self._check(self.lib.kid_fold_halo_self(self.h, int(width), int(bool(swap_slots))), "kid_fold_halo_self")
+
     # ---- restart files (icebergs_fms2io.F90:124-631, 663-1049) ----
     def write_restart(self, directory):
         self._check(self.lib.kid_write_restart(self.h, str(directory).encode()), "kid_write_restart")

@@ -30,6 +30,7 @@ SYMBOLS = [
     "kid_buffer_width", "kid_pack_emigrants", "kid_unpack_immigrants", "kid_pack_emigrants_pair", "kid_unpack_immigrants_pair",
     "kid_pack_halo_bergs_pair", "kid_halo_berg_count",
     "kid_calculate_mass_on_ocean", "kid_halo_plane_count", "kid_halo_buffer_count", "kid_pack_halo_pair", "kid_unpack_halo_pair",
+    "kid_unpack_halo_fold", "kid_fold_halo_self",
 ]
 
 
@@ -112,6 +113,8 @@ def load():
     lib.kid_halo_buffer_count.argtypes = [H, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     lib.kid_pack_halo_pair.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
     lib.kid_unpack_halo_pair.argtypes = [H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.kid_unpack_halo_fold.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+    lib.kid_fold_halo_self.argtypes = [H, C.c_int32, C.c_int32]
     lib.kid_read_restart.argtypes = [H, C.c_char_p]
     lib.kid_upload_bergs.argtypes = [H, C.POINTER(T.BergSoA)]
     lib.kid_step_prepare.argtypes = [H, C.POINTER(C.c_void_p)]

@@ -300,7 +300,18 @@ int kid_halo_berg_count(kid_handle *h, int64_t *n);   /* resident halo rows (ali
  * caller orders its own work behind the handle's stream.  Otherwise the strips go through a pinned staging buffer: the pack call
  * returns when the data are in buf_hi / buf_lo, the unpack call when from_lo / from_hi may be reused.
  * Not covered: find_melt_using_spread_mass on tiles (its two extra gathers inside kid_step_local would need the same update),
- * the parity swap of a tripolar fold (IB:6110-6122), the forcing planes (the host owns them). */
+ * the forcing planes (the host owns them).
+ *
+ * The tripolar north fold.  A tile of the top row has no north neighbour; its rows jec+1 .. jec+w lie beyond the fold and hold
+ * what its mirror partner's rows jec .. jec-w+1 hold, turned by 180 degrees (FMS: halo(i, nj+k) = field(ni+1-i, nj+1-k) for a
+ * centred scalar), with the nine slots of every group mirrored through the centre (IB:6110-6122: 1<->9, 2<->8, 3<->7, 4<->6).
+ * The sending side is kid_pack_halo_pair(h, 1, w, buf_hi, NULL, ...) as it stands; the caller moves buf_hi to the partner.
+ *   kid_unpack_halo_fold: element (plane 9 q + s, strip row r, strip column c) of the partner's strip goes to row jec + w - r,
+ *       column (isc-w) + (nic+2w-1-c) and, with swap_slots != 0, to plane 9 q + (8 - s); swap_slots == 0 keeps the plane
+ *       (old_bug_rotated_weights = T).  Call it after the east/west pass, next to the kid_unpack_halo_pair of the south strip.
+ *   kid_fold_halo_self: the same for a handle that owns the whole zonal width and so is its own partner: planes to planes, no buffer.
+ * The widths kid_unpack_halo_pair refuses and a NULL from_fold: KID_EINVAL; so is either call while halo rows are resident.
+ * The caller says whether to swap: the library does not read old_bug_rotated_weights here. */
 /* calculate_mass_on_ocean (IB:4984-...), the spreading half of kid_create_gridded_icebergs_fields: zero the 36 on-ocean planes,
  * the spreading launch (with reproducible sums: its fold too), NO gather.  kid_step_gather is the other half. */
 int kid_calculate_mass_on_ocean(kid_handle *h);
@@ -308,6 +319,8 @@ int kid_halo_plane_count(kid_handle *h, int32_t *nplanes);   /* 9 (mass_on_ocean
 int kid_halo_buffer_count(kid_handle *h, int32_t axis, int32_t width, int64_t *count);   /* doubles per direction */
 int kid_pack_halo_pair(kid_handle *h, int32_t axis, int32_t width, double *buf_hi, double *buf_lo, int32_t on_device);
 int kid_unpack_halo_pair(kid_handle *h, int32_t axis, int32_t width, const double *from_lo, const double *from_hi, int32_t on_device);
+int kid_unpack_halo_fold(kid_handle *h, int32_t width, const double *from_fold, int32_t swap_slots, int32_t on_device);
+int kid_fold_halo_self(kid_handle *h, int32_t width, int32_t swap_slots);
 
 /* kid_set_forcing_device + kid_zero_accumulators for the step about to start, as one per-cell launch (fields == NULL
  * keeps the current forcing and only zeroes); the following kid_step_local does not zero again. */
