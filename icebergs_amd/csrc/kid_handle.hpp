@@ -140,6 +140,8 @@ struct kid_handle {
   double *d_spread_mass_old = nullptr;   // grd%spread_mass_old (find_melt_using_spread_mass, IB:5495-5497) + spread_mass_tmp; the handle's own or the caller's (kid_bind_spread_mass_old)
   double *d_spread_mass_old_own = nullptr;
   bool have_static = false, have_forcing = false, have_planes = false;  // have_planes: d_forcing holds all eleven planes
+  bool have_centres = false;   // kid_set_static_grid was given lonc and latc (optional there; the cell search walks on them)
+  int restart_locate = 0;      // kid_set_restart_locate: 0 kid_read_restart trusts the file's ine, jne; 1, 2 it searches (kid_locate.inc)
   double *d_calv_state = nullptr, *d_calv_scal = nullptr, *d_calv_part = nullptr; unsigned char *d_calv_flag = nullptr; int2 *d_calv_list = nullptr; double *calv_host = nullptr; kid_calving_params calv_params{};  // kid_calving (kid_calving.inc)
   bool calving_on = false, calving_first_call = true, rmean_init = false, rmean_hflx_init = false;
   double *d_ingest_stage = nullptr; size_t ingest_stage_count = 0; unsigned long long *d_ingest_key = nullptr;  // kid_ingest_forcing

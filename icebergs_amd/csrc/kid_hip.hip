@@ -598,6 +598,7 @@ int kid_set_static_grid(kid_handle *h, const double *const fields[KID_NGRID_STAT
     KID_HIP(h, hipMemcpyAsync(h->d_static[k], fields[k], h->ncell * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
   h->have_static = true; h->bond_ext_valid = false;
+  h->have_centres = fields[KID_G_LONC] && fields[KID_G_LATC];
   int rc = pack_static(h);
   if (rc) return rc;
   const double *none[KID_NFORCING] = {};
@@ -953,6 +954,7 @@ int kid_profile_get(kid_handle *h, double *berg_ms, int64_t *launches, double *a
 
 }  // extern "C"
 
+#include "kid_locate.inc"
 #include "kid_restart.inc"
 #include "kid_traj.inc"
 #include "kid_migrate.inc"

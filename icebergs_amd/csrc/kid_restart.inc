@@ -505,6 +505,7 @@ int kid_write_restart(kid_handle *h, const char *dir) {
 // read_restart_bergs (IO2:663-1049) + read_restart_calving into the handle: bergs whose (ine, jne) lies outside the
 // computational domain are not this rank's (IO2:880-884), bergs in cells of zero area are dropped as grounded
 // (IO2:948-955); xi, yj are recomputed on the device.  calving.res.nc is read when it exists and the calving source is on.
+// With kid_set_restart_locate (ignore_ij_restart) the cells come from the positions instead (kid_locate.inc); the rest is the same.
 int kid_read_restart(kid_handle *h, const char *dir) {
   if (!h || !dir) return KID_EINVAL;
   if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
@@ -526,6 +527,10 @@ int kid_read_restart(kid_handle *h, const char *dir) {
   soa.id = id.data();
   int rc = kid_restart_read_bergs(path.c_str(), &soa, nfile);
   if (rc) { h->err = "cannot read " + path; return rc; }
+  if (h->restart_locate) {   // ignore_ij_restart (IO2:885-890): the file's ine, jne are not read; each berg's cell is searched from lon, lat
+    rc = restart_locate_cells(h, f64[KID_B_LON].data(), f64[KID_B_LAT].data(), i32[KID_BI_INE].data(), i32[KID_BI_JNE].data(), nfile);
+    if (rc) return rc;
+  }
   std::vector<double> area(h->ncell);
   KID_HIP(h, hipMemcpy(area.data(), h->d_static[KID_G_AREA], h->ncell * sizeof(double), hipMemcpyDeviceToHost));
   const kid_grid_desc &d = h->gd;

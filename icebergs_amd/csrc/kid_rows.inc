@@ -155,6 +155,12 @@ static void rows_moved(kid_handle *h, bool dead_last) { rows_orders_stale(h); h-
 static void rows_truncated(kid_handle *h, int64_t n) { rows_orders_stale(h); h->tail_valid = false; h->n = n; }
 // a per-berg launch or a pack call may have killed rows anywhere: the dead are no longer exactly the tail
 static void rows_killed(kid_handle *h) { h->tail_valid = false; }
+// kid_locate_bergs: every live row has a new cell and new xi, yj (whatever was uploaded there), the rows no cell took are dead
+static void rows_located(kid_handle *h) {
+  rows_orders_stale(h);
+  rows_killed(h);
+  h->uploaded_nonzero[KID_B_XI] = true; h->uploaded_nonzero[KID_B_YJ] = true;
+}
 // calving, footloose calving, immigrants: rows [n, n + m) were written.  records: the m wire records they were decoded from
 // (kid_rows_plan.hpp), or NULL for rows a kernel wrote -- those may hold anything in any field.  The kernels bound their own
 // writes by the capacity and count on: more rows than room leaves the handle full and is KID_ECAPACITY with `full` as message.

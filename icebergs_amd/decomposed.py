@@ -119,6 +119,13 @@ class HipTile:
     def set_auto_reserve(self, min_free, growth=1.5, max_capacity=0):
         self.ib.set_auto_reserve(min_free, growth, max_capacity)
 
+    # cells from positions, per tile: a tile that reads a global file keeps the bergs of its own computational domain
+    def locate_bergs(self, mode="search"):
+        return self.ib.locate_bergs(mode)
+
+    def set_restart_locate(self, mode):
+        self.ib.set_restart_locate(mode)
+
 
 class TileExchange:
     """ranks laid out as an ntx x nty array of tiles, rank = ty * ntx + tx (x fastest, like the reference's domain layout);

@@ -45,6 +45,7 @@ module kid_hip_mod
   public :: kid_calculate_mass_on_ocean, kid_halo_plane_count, kid_halo_buffer_count, kid_pack_halo_pair, kid_unpack_halo_pair
   public :: kid_unpack_halo_fold, kid_fold_halo_self
   public :: kid_capacity, kid_reserve, kid_set_auto_reserve
+  public :: kid_locate_bergs, kid_set_restart_locate
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -137,6 +138,19 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_char
       type(c_ptr), value :: h
       character(kind=c_char), intent(in) :: dir(*)
+    end function
+    !> cells from positions (ignore_ij_restart, IO2:876-891): mode 1 find_cell_by_search, 2 find_cell; counts = found, not on
+    !! this grid, grounded.  kid_set_restart_locate: mode 0 (kid_read_restart trusts the file's ine, jne), 1 or 2
+    integer(c_int) function kid_locate_bergs(h, mode, counts) bind(C, name='kid_locate_bergs')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int), value :: mode
+      integer(c_int64_t), intent(out) :: counts(3)
+    end function
+    integer(c_int) function kid_set_restart_locate(h, mode) bind(C, name='kid_set_restart_locate')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+      integer(c_int), value :: mode
     end function
     !> record_posn (FW:5328-5498) on the device and iceberg_trajectories.nc (icebergs_fms2io.F90:1631-2103) from its records
     integer(c_int) function kid_set_traj_params(h, tp) bind(C, name='kid_set_traj_params')

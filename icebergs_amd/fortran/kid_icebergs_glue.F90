@@ -189,6 +189,8 @@ contains
   !! the lists' one convenience back: the handle grows before calving, footloose children or a larger upload would overflow it
   !! (kid_set_auto_reserve), and the staging arrays follow.  With both absent a population that outgrows `capacity` stops the run.
   !! Restart reading stays with the caller (kid_read_restart, or kid_glue_add_berg + form_a_bond for a population of its own);
+  !! the namelist's ignore_ij_restart / use_slow_find are handed to the handle here (kid_set_restart_locate), so that
+  !! kid_read_restart of a file from another grid or layout, or one with positions only, searches each berg's cell (IO2:876-891);
   !! call kid_icebergs_init_bonds after the population is in the lists for the bonded / DEM tail of icebergs_init (IB:141-176).
   subroutine kid_icebergs_init(bergs, gni, gnj, layout, io_layout, axes, dom_x_flags, dom_y_flags, dt, year, yearday, &
                                ice_lon, ice_lat, ice_wet, ice_dx, ice_dy, ice_area, cos_rot, sin_rot, ocean_depth, maskmap, fractional_area, &
@@ -455,6 +457,9 @@ contains
     call kid_check(kid_create(gd, par, cap, int(dev, c_int), bergs%h), bergs%h, 'kid_create')
     do f = 1, KID_NGRID_STATIC ; pst(f) = c_loc(st(isd, jsd, f)) ; enddo
     call kid_check(kid_set_static_grid(bergs%h, pst), bergs%h, 'kid_set_static_grid')
+    ! ignore_ij_restart (IO2:876-891): kid_read_restart finds every berg's cell from its position, by find_cell with
+    ! use_slow_find (the namelist's default) and by find_cell_by_search without
+    call kid_check(kid_set_restart_locate(bergs%h, int(merge(merge(2, 1, use_slow_find), 0, ignore_ij_restart), c_int)), bergs%h, 'kid_set_restart_locate')
     if (present(auto_reserve_growth) .or. present(auto_reserve_min_free)) then
       bergs%auto_reserve_growth = 1.5_c_double ; if (present(auto_reserve_growth)) bergs%auto_reserve_growth = auto_reserve_growth
       ar_min_free = 0 ; if (present(auto_reserve_min_free)) ar_min_free = auto_reserve_min_free

@@ -332,6 +332,26 @@ class Icebergs:
     def read_restart(self, directory):
         self._check(self.lib.kid_read_restart(self.h, str(directory).encode()), "kid_read_restart")
 
+    # ---- cells from positions: ignore_ij_restart / use_slow_find (IO2:876-891; include/kid.h) ----
+    LOCATE_MODES = {"search": 1, "scan": 2}
+
+    def locate_bergs(self, mode="search"):
+        """the cell and xi, yj of every live resident berg from its lon, lat: "search" is find_cell_by_search (FW:5710-5842),
+        "scan" is find_cell (FW:6011-6041).  Bergs no cell of the computational domain holds, or whose cell has no area, become
+        dead rows.  Returns {"found", "lost", "grounded"}."""
+        if mode not in self.LOCATE_MODES:
+            raise ValueError("locate_bergs: mode is 'search' or 'scan', not %r" % (mode,))
+        c = (C.c_int64 * 3)()
+        self._check(self.lib.kid_locate_bergs(self.h, self.LOCATE_MODES[mode], c), "kid_locate_bergs")
+        return {"found": int(c[0]), "lost": int(c[1]), "grounded": int(c[2])}
+
+    def set_restart_locate(self, mode):
+        """read_restart with ignore_ij_restart: None (the default) trusts the file's ine, jne; "search" or "scan" finds every
+        berg's cell from its position, so a handle keeps the bergs of its own computational domain out of any file"""
+        if mode is not None and mode not in self.LOCATE_MODES:
+            raise ValueError("set_restart_locate: mode is None, 'search' or 'scan', not %r" % (mode,))
+        self._check(self.lib.kid_set_restart_locate(self.h, 0 if mode is None else self.LOCATE_MODES[mode]), "kid_set_restart_locate")
+
     # ---- calving source (IB:5203-5231, accumulate_calving IB:6153, calve_icebergs IB:6225) ----
     def set_calving_params(self, cp):
         self._calv_params = cp

@@ -25,6 +25,7 @@ SYMBOLS = [
     "kid_ingest_forcing", "kid_get_forcing",
     "kid_set_calving_params", "kid_set_calving_state", "kid_get_calving_state", "kid_calving", "kid_get_calving",
     "kid_restart_write_bergs", "kid_restart_count_bergs", "kid_restart_read_bergs", "kid_restart_write_bonds", "kid_restart_read_bonds", "kid_write_restart", "kid_read_restart", "kid_bergs_chksum",
+    "kid_locate_bergs", "kid_set_restart_locate",
     "kid_set_traj_params", "kid_record_posn", "kid_num_traj_records", "kid_write_trajectories",
     "kid_num_bond_traj_records", "kid_write_bond_trajectories",
     "kid_buffer_width", "kid_pack_emigrants", "kid_unpack_immigrants", "kid_pack_emigrants_pair", "kid_unpack_immigrants_pair",
@@ -116,6 +117,10 @@ def load():
     lib.kid_unpack_halo_fold.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.kid_fold_halo_self.argtypes = [H, C.c_int32, C.c_int32]
     lib.kid_read_restart.argtypes = [H, C.c_char_p]
+    older = ("kid_rebin_fused_count", "kid_locate_bergs", "kid_set_restart_locate")   # absent from an older build loaded through KID_HIP_SO for an A/B run
+    if hasattr(lib, "kid_locate_bergs"):
+        lib.kid_locate_bergs.argtypes = [H, C.c_int, C.POINTER(C.c_int64)]
+        lib.kid_set_restart_locate.argtypes = [H, C.c_int]
     lib.kid_upload_bergs.argtypes = [H, C.POINTER(T.BergSoA)]
     lib.kid_step_prepare.argtypes = [H, C.POINTER(C.c_void_p)]
     lib.kid_set_side_stream.argtypes = [H, C.c_void_p, C.c_int]
@@ -160,7 +165,7 @@ def load():
     lib.kid_profile_enable.argtypes = [H, C.c_int]
     lib.kid_profile_get.argtypes = [H, dp, C.POINTER(C.c_int64), dp]
     for name in SYMBOLS:
-        if name == "kid_rebin_fused_count" and not hasattr(lib, name):   # a diagnostic: an older build stays loadable for A/B runs
+        if name in older and not hasattr(lib, name):   # an older build stays loadable for A/B runs; calling what it lacks is an AttributeError
             continue
         if name not in ("kid_version", "kid_last_error", "kid_sizeof", "kid_footloose_uniform"):
             getattr(lib, name).restype = C.c_int

@@ -203,6 +203,26 @@ int kid_restart_read_bonds(const char *path, const kid_berg_soa *bergs, kid_bond
  * recomputed on the device from (lon, lat, ine, jne) (IO2:945) */
 int kid_write_restart(kid_handle *h, const char *dir);
 int kid_read_restart(kid_handle *h, const char *dir);
+/* ---- a berg's cell from its position: ignore_ij_restart / use_slow_find (IO2:876-891) ----
+ * mode 1 is find_cell_by_search (FW:5710-5842: the walk over the cell centres from the nearest inset corner, find_better_min and
+ * find_cell_loc on stagnation, find_cell when the moves run out), mode 2 is find_cell (FW:6011-6041: the structured-grid guess,
+ * then the scan of the computational domain, j outer, i inner, first hit).  One lane per berg; the scan is shared by the wave
+ * (csrc/kid_locate.inc).  A berg the reference's path does not find is not found here either.  The grid needs lonc / latc and a
+ * halo of one cell (the walk reads the centres one cell beyond the computational domain): KID_EINVAL otherwise.
+ *
+ * kid_locate_bergs: on the live resident rows, from their lon, lat: writes ine, jne and xi, yj (pos_within_cell, IO2:947).  A row
+ * that no cell of the computational domain holds, or whose cell has area 0 (grounded, IO2:950-957), becomes dead -- its cell
+ * set to (isc, jsc), so that a decomposed handle does not take it for a berg waiting to be packed -- and leaves with the next
+ * kid_num_bergs tail drop, compaction or re-binning.  counts (may be NULL) = {found, not on this grid, grounded}.  No other
+ * field changes.  Refused with nothing written: mode outside {1, 2} and no static grid (KID_EINVAL), halo rows resident
+ * (KID_EINVAL), bond tables on the handle (KID_EUNSUPPORTED: bonds keep their rows; locate first, then kid_upload_bonds). */
+int kid_locate_bergs(kid_handle *h, int mode, int64_t counts[3]);
+/* kid_read_restart with ignore_ij_restart: mode 0 (the default) trusts the file's ine, jne; with 1 or 2 they are ignored and
+ * every berg of the file is searched by that mode in temporary device blocks sized by the file (freed before the call
+ * returns), after which the read goes on as before: a berg that was not found fails the domain test, ids of a legacy file
+ * are handed out in file order before the grounded filter.  A handle that reads one global file keeps the bergs of its own
+ * computational domain.  Another mode: KID_EINVAL. */
+int kid_set_restart_locate(kid_handle *h, int mode);
 /* bergs_chksum (FW:6889-6987: the "write_restart berg chksum=.. chksum2=.. chksum3=.. chksum4=.. chksum5=.. #=.." line of
  * icebergs_save_restart, IB:8145, which the reference's regression tests record) on the resident population:
  * out[0..4] = chksum, chksum2, chksum3, chksum4, chksum5 as the default integers the reference prints, out[5] = #, the number
