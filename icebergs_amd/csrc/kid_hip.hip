@@ -14,6 +14,8 @@
 //                                one body.  HBM-streaming on the SoA, grid served from L2 / Infinity Cache.
 //   gather_kernel              : per cell, the 9-point gather of sum_up_spread_fields (IB:6126-6138) + ustar.
 #include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -419,7 +421,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   if (getenv("KID_MTS_NO_GRAPH")) h->use_graph = false;  // A/B switch for measurements
   h->dbg.stable_resort = getenv("KID_STABLE_RESORT") != nullptr; h->dbg.no_plain_build = getenv("KID_NO_PLAIN_BUILD") != nullptr;
   h->dbg.fl_unfused = getenv("KID_FL_UNFUSED") != nullptr; h->dbg.new_order_unfused = getenv("KID_NEW_ORDER_UNFUSED") != nullptr;
-  h->dbg.rebin_eager = getenv("KID_REBIN_EAGER") != nullptr;
+  h->dbg.rebin_eager = getenv("KID_REBIN_EAGER") != nullptr; h->dbg.chksum_timing = getenv("KID_CHKSUM_TIMING") != nullptr;
   h->dbg.mts_always_label = getenv("KID_MTS_ALWAYS_LABEL") != nullptr; h->dbg.mts_no_fused = getenv("KID_MTS_NO_FUSED") != nullptr;
   if (const char *e = getenv("KID_MTS_FUSED_BLOCKS_CAP")) h->dbg.mts_fused_blocks_cap = atoi(e);
   if (const char *e = getenv("KID_MTS_POLL_LIMIT")) h->dbg.mts_poll_limit = atoi(e);
@@ -615,6 +617,7 @@ int kid_set_forcing(kid_handle *h, const double *const fields[KID_NFORCING]) {
   for (int k = 0; k < KID_NFORCING; ++k) {
     if (!fields[k]) continue;  // NULL keeps the previous plane
     KID_HIP(h, hipMemcpyAsync(h->d_forcing[k], fields[k], h->ncell * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->forcing_held[k] = true;
   }
   h->have_forcing = true;
   { bool all = true; for (int k = 0; k < KID_NFORCING; ++k) all = all && (fields[k] || h->have_planes); h->have_planes = all; }
@@ -632,7 +635,7 @@ int kid_set_forcing_device(kid_handle *h, const double *const fields[KID_NFORCIN
   // The per-cell records are built straight from the caller's planes; only ssh is also kept as a plane (the
   // grounding_fraction path of the mass spreading reads it, IB:3942).
   if (fields[KID_F_SSH])
-    KID_HIP(h, hipMemcpyAsync(h->d_forcing[KID_F_SSH], fields[KID_F_SSH], h->ncell * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    { KID_HIP(h, hipMemcpyAsync(h->d_forcing[KID_F_SSH], fields[KID_F_SSH], h->ncell * sizeof(double), hipMemcpyDeviceToDevice, h->stream)); h->forcing_held[KID_F_SSH] = true; }
   h->have_forcing = true;
   return pack_forcing(h, fields);
 }
@@ -652,6 +655,7 @@ int kid_step_prepare(kid_handle *h, const double *const fields[KID_NFORCING]) {
   }
   PrepExtras ex;
   ex.ssh_copy = (src[KID_F_SSH] && src[KID_F_SSH] != h->d_forcing[KID_F_SSH]) ? h->d_forcing[KID_F_SSH] : nullptr;
+  if (ex.ssh_copy) h->forcing_held[KID_F_SSH] = true;
   ex.acc = h->d_acc; ex.zero_planes = nacc_active(h);
   ex.cnt0 = h->d_redo_cnt[0][h->redo_parity]; ex.cnt1 = h->d_redo_cnt[1][h->redo_parity];
   h->have_forcing = true;
@@ -961,3 +965,4 @@ int kid_profile_get(kid_handle *h, double *berg_ms, int64_t *launches, double *a
 #include "kid_halo_bergs.inc"
 #include "kid_halo.inc"
 #include "kid_chksum.inc"
+#include "kid_chksum_device.inc"

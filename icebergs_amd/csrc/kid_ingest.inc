@@ -215,6 +215,7 @@ int kid_ingest_forcing(kid_handle *h, const kid_forcing_in *in) {
   hipLaunchKernelGGL(ingest_scrub_kernel, dim3(nb), dim3(256), 0, h->stream, a);
   KID_HIP(h, hipGetLastError());
   h->have_forcing = true; h->have_planes = true;
+  for (int k = 0; k < KID_NFORCING; ++k) h->forcing_held[k] = true;
   const double *none[KID_NFORCING] = {};
   const int rc = pack_forcing(h, none);  // the per-cell records the berg kernels read
   if (rc) return rc;

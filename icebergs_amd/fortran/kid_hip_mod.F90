@@ -46,6 +46,7 @@ module kid_hip_mod
   public :: kid_unpack_halo_fold, kid_fold_halo_self
   public :: kid_capacity, kid_reserve, kid_set_auto_reserve
   public :: kid_locate_bergs, kid_set_restart_locate
+  public :: kid_grd_chksum, kid_bergs_chksum_device, kid_checksum_gridded, kid_chk_label, kid_chk_is_3d
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -133,6 +134,21 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int64_t
       type(c_ptr), value :: h
       integer(c_int64_t), intent(out) :: chk(6)
+    end function
+    !> the same six integers from the resident state, without the download; per_cell: c_loc of a type(kid_grd_chksum) for the
+    !! '# of bergs/cell' record (FW:6978-6979), or c_null_ptr
+    integer(c_int) function kid_bergs_chksum_device(h, chk, per_cell) bind(C, name='kid_bergs_chksum_device')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), intent(out) :: chk(6)
+      type(c_ptr), value :: per_cell
+    end function
+    !> checksum_gridded (FW:6685-6758) on the device: recs(KID_NCHK), record KID_CHK_x + 1 is field x; n_out = size(recs)
+    integer(c_int) function kid_checksum_gridded(h, recs, n_out) bind(C, name='kid_checksum_gridded')
+      import :: c_int, c_ptr, c_int32_t, kid_grd_chksum
+      type(c_ptr), value :: h
+      type(kid_grd_chksum), intent(out) :: recs(*)
+      integer(c_int32_t), value :: n_out
     end function
     integer(c_int) function kid_read_restart(h, dir) bind(C, name='kid_read_restart')
       import :: c_int, c_ptr, c_char
@@ -579,6 +595,27 @@ contains
     do k = 1, n
       msg(k:k) = chars(k)
     end do
+  end function
+
+  !> The label checksum_gridded prints for record k = KID_CHK_x + 1 (FW:6694-6756, tests/golden/checksum_gridded_names.json)
+  function kid_chk_label(k) result(txt)
+    integer, intent(in) :: k
+    character(len=18) :: txt
+    character(len=18), parameter :: labels(KID_NCHK) = [character(len=18) :: &
+      'uo', 'vo', 'ua', 'va', 'ui', 'vi', 'ssh', 'sst', 'sss', 'hi', 'cn', 'calving', 'calving_hflx', &
+      'mass', 'mass_on_ocean', 'area_on_ocean', 'Uvel_on_ocean', 'Vvel_on_ocean', 'stored_ice', 'rmean_calving', &
+      'rmean_calving_hflx', 'stored_heat', 'melt_b', 'melt_e', 'melt_v', 'bergy_src', 'bergy_melt', 'bergy_mass', &
+      'fl_bits_src', 'fl_bits_melt', 'fl_bits_mass', 'fl_bergy_bits_mass', 'spread_mass', 'spread_area', 'u_iceberg', &
+      'v_iceberg', 'spread_uvel', 'spread_vvel', 'ustar_iceberg', 'varea', 'floating_melt', 'berg_melt', 'melt_by_class', &
+      'melt_b_fl', 'melt_e_fl', 'melt_v_fl', 'fl_parent_melt', 'fl_child_melt', &
+      'lon', 'lat', 'lonc', 'latc', 'dx', 'dy', 'area', 'msk', 'cos', 'sin', 'depth']
+    txt = labels(k)
+  end function
+
+  !> Whether record k is one of the fields grd_chksum3 takes (the *_on_ocean planes, stored_ice, melt_by_class)
+  logical function kid_chk_is_3d(k)
+    integer, intent(in) :: k
+    kid_chk_is_3d = (k >= KID_CHK_MASS_ON_OCEAN + 1 .and. k <= KID_CHK_STORED_ICE + 1) .or. k == KID_CHK_MELT_BY_CLASS + 1
   end function
 
   !> Abort on a non-zero status: the reference's error_mesg(...,FATAL) convention (e.g. icebergs.F90:3207)

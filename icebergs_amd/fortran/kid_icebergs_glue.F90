@@ -29,7 +29,7 @@ module kid_icebergs_glue
   public :: iceberg, bond, linked_list, kid_glue, inorder, insert_berg_into_list, kid_glue_init, kid_glue_set_calving, kid_glue_add_berg, kid_glue_count, &
             kid_glue_flatten, kid_glue_unflatten, kid_glue_clear_lists, kid_glue_end, kid_icebergs_run, kid_icebergs_init, kid_read_icebergs_nml, &
             kid_icebergs_init_bonds, kid_icebergs_run_local, kid_icebergs_run_finish, kid_exchange_sum, row_to_node, node_to_row, form_a_bond, kid_glue_find_berg, KID_CYCLIC_GLOBAL_DOMAIN, &
-            kid_icebergs_stock_pe, kid_icebergs_incr_mass, kid_glue_reserve
+            kid_icebergs_stock_pe, kid_icebergs_incr_mass, kid_glue_reserve, kid_glue_checksums
   !> FMS's mpp_domains flag for a zonally periodic global domain (mpp_parameter_mod), as DRV:44 passes it in dom_x_flags
   integer, parameter :: KID_CYCLIC_GLOBAL_DOMAIN = 2
 
@@ -1034,11 +1034,13 @@ contains
     fi%vel_stagger = vel_stagger ; fi%stress_stagger = str_stagger
     fi%tau_is_velocity = merge(1, 0, bergs%tau_is_velocity) ; fi%cyclic_x = merge(1, 0, bergs%gd%Lx > 0.) ; fi%on_device = 0 ; fi%pad = 0
     call kid_check(kid_ingest_forcing(bergs%h, fi), bergs%h, 'kid_ingest_forcing')
+    if (debug) call kid_glue_checksums(bergs, 'top of s/r run')                                ! IB:5385-5386
     ! calving source, IB:5203-5231, 5388, 5403
     if (bergs%calving_on) then
       ci%calving = c_loc(calving) ; ci%calving_hflx = c_loc(calving_hflx) ; ci%on_device = 0 ; ci%pad = 0
       call kid_check(kid_calving(bergs%h, ci, cscal), bergs%h, 'kid_calving')
     endif
+    if (debug) call kid_glue_checksums(bergs, 's/r run after calving')                         ! IB:5404-5405
     ! the hot path, IB:5423-5512: this GPU's bergs
     call kid_check(kid_step_local(bergs%h), bergs%h, 'kid_step_local')
   end subroutine kid_icebergs_run_local
@@ -1062,6 +1064,7 @@ contains
     j0 = bergs%gd%jsc - bergs%gd%jsd + 1 ; j1 = bergs%gd%jec - bergs%gd%jsd + 1
     bergs%gcalv = 0. ; bergs%ghflx = 0.
     if (bergs%calving_on) call kid_check(kid_get_calving(bergs%h, c_loc(bergs%gcalv), c_loc(bergs%ghflx)), bergs%h, 'kid_get_calving')
+    if (debug) call kid_glue_checksums(bergs, 'end of s/r run')   ! IB:5881-5882 (what follows writes the coupler's arrays only)
     if (bergs%passive_mode) return
     where (bergs%area(i0:i1, j0:j1) > 0.)
       calving(:,:) = bergs%gcalv(i0:i1, j0:j1) / bergs%area(i0:i1, j0:j1) + bergs%acc(i0:i1, j0:j1, KID_A_FLOATING_MELT+1)
@@ -1079,6 +1082,35 @@ contains
       if (associated(area_berg)) area_berg(:,:) = bergs%outp(i0:i1, j0:j1, KID_O_SPREAD_AREA+1)
     endif
   end subroutine kid_icebergs_run_finish
+
+  !> What the reference prints under `debug` at one point of icebergs_run: bergs_chksum (FW:6975) with its '# of bergs/cell'
+  !! record (FW:6978-6979), then checksum_gridded (FW:6691) with one line per field the handle holds (FW:6876, 6817), in the
+  !! reference's formats.  Everything is computed on the resident state (kid_bergs_chksum_device, kid_checksum_gridded).
+  subroutine kid_glue_checksums(g, label)
+    type(kid_glue), intent(inout) :: g
+    character(len=*), intent(in) :: label
+    integer(c_int64_t) :: chk(6)
+    type(kid_grd_chksum), target :: cell
+    type(kid_grd_chksum) :: recs(KID_NCHK)
+    integer :: k
+    call kid_check(kid_bergs_chksum_device(g%h, chk, c_loc(cell)), g%h, 'kid_bergs_chksum_device')
+    write(*,'("KID, bergs_chksum: ",a18,6(x,a,"=",i22))') label, 'chksum', chk(1), 'chksum2', chk(2), 'chksum3', chk(3), &
+      'chksum4', chk(4), 'chksum5', chk(5), '#', chk(6)
+    call print_record(2, '# of bergs/cell', cell)
+    write(*,'(2a)') 'KID: checksumming gridded data @ ', trim(label)
+    call kid_check(kid_checksum_gridded(g%h, recs, int(KID_NCHK, c_int32_t)), g%h, 'kid_checksum_gridded')
+    do k = 1, KID_NCHK
+      if (recs(k)%present /= 0) call print_record(merge(3, 2, kid_chk_is_3d(k)), trim(kid_chk_label(k)), recs(k))
+    enddo
+  contains
+    subroutine print_record(dims, txt, r)
+      integer, intent(in) :: dims
+      character(len=*), intent(in) :: txt
+      type(kid_grd_chksum), intent(in) :: r
+      write(*,'("KID, grd_chksum",i1,": ",a18,2(x,a,"=",i22),5(x,a,"=",es16.9))') dims, txt, 'chksum', r%chksum, 'chksum2', r%chksum2, &
+        'min', r%minv, 'max', r%maxv, 'mean', r%mean, 'rms', r%rms, 'sd', r%sd
+    end subroutine print_record
+  end subroutine kid_glue_checksums
 
   !> icebergs_stock_pe (IB:8102-8133) behind its argument list: index = KID_STOCK_WATER or KID_STOCK_HEAT (FMS's ISTOCK_WATER,
   !! ISTOCK_HEAT); any other index leaves value = 0., the reference's `case default`.  A device reduction over the resident bergs

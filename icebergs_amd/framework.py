@@ -19,6 +19,39 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _chk_record(rec):
+    return {name: getattr(rec, name) for name, _ in T.GrdChksum._fields_ if name != "pad_"}
+
+
+def _a18(txt):
+    """Fortran's a18: the leftmost 18 characters, or the text right-justified in 18 columns"""
+    return txt[:18].rjust(18)
+
+
+def _es16_9(x):
+    """Fortran's es16.9 (a three-digit exponent drops the letter: 1.000000000+100)"""
+    if x != x:
+        return "NaN".rjust(16)
+    if x in (float("inf"), float("-inf")):
+        return ("Infinity" if x > 0 else "-Infinity").rjust(16)
+    mant, exp = ("%.9E" % x).split("E")
+    return (mant + ("E" + exp if len(exp) == 3 else exp)).rjust(16)
+
+
+def format_bergs_chksum(label, six):
+    """FW:6975: '("KID, bergs_chksum: ",a18,6(x,a,"=",i22))'"""
+    names = ("chksum", "chksum2", "chksum3", "chksum4", "chksum5", "#")
+    return "KID, bergs_chksum: " + _a18(label) + "".join(" %s=%22d" % (n, v) for n, v in zip(names, six))
+
+
+def format_grd_chksum(label, rec, three_d=False):
+    """FW:6876 (grd_chksum2) and FW:6817 (grd_chksum3); the i8 group that ends grd_chksum2's format has no item and prints nothing"""
+    head = "KID, grd_chksum%d: " % (3 if three_d else 2)
+    ints = "".join(" %s=%22d" % (n, rec[n]) for n in ("chksum", "chksum2"))
+    reals = "".join(" %s=%s" % (n, _es16_9(rec[k])) for n, k in (("min", "minv"), ("max", "maxv"), ("mean", "mean"), ("rms", "rms"), ("sd", "sd")))
+    return head + _a18(label) + ints + reals
+
+
 _LIVE = weakref.WeakSet()
 
 
@@ -513,6 +546,31 @@ class Icebergs:
         out = (C.c_int64 * 6)()
         self._check(self.lib.kid_bergs_chksum(self.h, out), "kid_bergs_chksum")
         return tuple(int(v) for v in out)
+
+    def bergs_chksum_device(self, per_cell=False):
+        """the same six integers from the resident state without the download (kid_bergs_chksum_device, include/kid.h); with
+        per_cell: (integers, record of the '# of bergs/cell' line as a dict of the members of kid_grd_chksum)"""
+        out, rec = (C.c_int64 * 6)(), T.GrdChksum()
+        self._check(self.lib.kid_bergs_chksum_device(self.h, out, C.byref(rec) if per_cell else None), "kid_bergs_chksum_device")
+        six = tuple(int(v) for v in out)
+        return (six, _chk_record(rec)) if per_cell else six
+
+    def checksum_gridded(self):
+        """checksum_gridded (FW:6685-6758) on the device: {label: record} in the reference's order (types.CHK_LABELS), a record
+        being the members of kid_grd_chksum as a dict"""
+        recs = (T.GrdChksum * T.NCHK)()
+        self._check(self.lib.kid_checksum_gridded(self.h, recs, T.NCHK), "kid_checksum_gridded")
+        return {label: _chk_record(recs[k]) for k, label in enumerate(T.CHK_LABELS)}
+
+    def checksum_report(self, label):
+        """the lines the reference prints under `debug` at one point of icebergs_run (bergs_chksum, its '# of bergs/cell' record,
+        then checksum_gridded: FW:6975, 6876, 6691, 6817), for the fields the handle holds"""
+        six, per_cell = self.bergs_chksum_device(per_cell=True)
+        lines = [format_bergs_chksum(label, six), format_grd_chksum("# of bergs/cell", per_cell), "KID: checksumming gridded data @ " + label.rstrip()]
+        for name, rec in self.checksum_gridded().items():
+            if rec["present"]:
+                lines.append(format_grd_chksum(name, rec, three_d=name in T.CHK_3D))
+        return lines
 
     # ---- budgets (icebergs_stock_pe IB:8102-8133, icebergs_incr_mass IB:6046-6074, the budget block IB:5702-5727) ----
     def stock(self, index):

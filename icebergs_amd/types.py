@@ -100,7 +100,23 @@ class BudgetOut(C.Structure):
     _fields_ = _parse_struct(_src, "kid_budget_out", ENUMS)
 
 
-BOND_F64_NAMES = [k[len("KID_BOND_"):].lower() for k, v in sorted(
+class GrdChksum(C.Structure):
+    _fields_ = _parse_struct(_src, "kid_grd_chksum", ENUMS)
+
+
+# checksum_gridded (FW:6694-6756): the label the reference prints for each record, in its order, and whether the field is 3-d
+CHK_LABELS = [
+    "uo", "vo", "ua", "va", "ui", "vi", "ssh", "sst", "sss", "hi", "cn", "calving", "calving_hflx",
+    "mass", "mass_on_ocean", "area_on_ocean", "Uvel_on_ocean", "Vvel_on_ocean", "stored_ice", "rmean_calving", "rmean_calving_hflx",
+    "stored_heat", "melt_b", "melt_e", "melt_v", "bergy_src", "bergy_melt", "bergy_mass", "fl_bits_src", "fl_bits_melt", "fl_bits_mass",
+    "fl_bergy_bits_mass", "spread_mass", "spread_area", "u_iceberg", "v_iceberg", "spread_uvel", "spread_vvel", "ustar_iceberg", "varea",
+    "floating_melt", "berg_melt", "melt_by_class", "melt_b_fl", "melt_e_fl", "melt_v_fl", "fl_parent_melt", "fl_child_melt",
+    "lon", "lat", "lonc", "latc", "dx", "dy", "area", "msk", "cos", "sin", "depth",
+]
+CHK_3D = ("mass_on_ocean", "area_on_ocean", "Uvel_on_ocean", "Vvel_on_ocean", "stored_ice", "melt_by_class")
+NCHK = ENUMS["KID_NCHK"]
+
+BOND_F64_NAMES =[k[len("KID_BOND_"):].lower() for k, v in sorted(
     ((k, v) for k, v in ENUMS.items() if k.startswith("KID_BOND_")), key=lambda kv: kv[1])]
 BERG_F64_NAMES = [k[len("KID_B_"):].lower() for k, v in sorted(
     ((k, v) for k, v in ENUMS.items() if k.startswith("KID_B_")), key=lambda kv: kv[1])]

@@ -229,6 +229,24 @@ int kid_set_restart_locate(kid_handle *h, int mode);
  * of bergs on the computational domain.  FMS's mpp_chksum is restated (wrap-around sum of bit patterns); see
  * csrc/kid_chksum.inc for the quirks that are reproduced on purpose. */
 int kid_bergs_chksum(kid_handle *h, int64_t out[6]);
+/* The same six integers, always identical to kid_bergs_chksum's on the same state, without the download: the traversal order
+ * is built on the device by stable radix passes (csrc/kid_chksum_device.inc), chksum, chksum2 and chksum5 are integer
+ * reductions there, and for chksum3 = chksum4 the device hands the host 16 bytes per berg of the computational domain (mass
+ * and time_hash * pos_hash, in traversal order) plus the per-cell counts: the logarithm is the host's std::log, so that the
+ * integers do not depend on which of the two routines computed them.  Same contract as kid_bergs_chksum: halo rows resident
+ * are refused, dead rows and live rows outside the computational domain do not count, n = 0 gives six zeros, bond tables may be
+ * resident.  per_cell (may be NULL) receives the record of the reference's '# of bergs/cell' line (FW:6978-6979): grd_chksum2
+ * of the plane of per-cell counts.  Temporary device blocks sized by the number of rows and by the grid, freed before return. */
+int kid_bergs_chksum_device(kid_handle *h, int64_t out[6], kid_grd_chksum *per_cell);
+/* checksum_gridded (FW:6685-6758): one record per field, out[KID_CHK_UO .. KID_CHK_DEPTH] in the reference's order, n_out >=
+ * KID_NCHK (else KID_EINVAL).  A plane is what kid_get_forcing, kid_get_calving, kid_get_calving_state and kid_get_accumulators
+ * would return at that moment, or the static grid; an accumulator plane that the step neither zeroes nor fills (footprint
+ * planes nobody reads, diagnostics that are off) reads as zeros; a field the handle does not hold (calving never configured,
+ * a forcing plane never given, lonc / latc not set) has present = 0 and zeros.  grd_chksum2 / grd_chksum3 (FW:6761-6886)
+ * over the computational domain; 3-d fields are the nine-slot *_on_ocean planes, stored_ice and melt_by_class.  Nothing is
+ * downloaded: two device sweeps over all fields, each a tree of fixed shape (no atomics), so two calls on the same state
+ * return the same bits; the mean, rms and sd differ from the reference's serial sums by rounding. */
+int kid_checksum_gridded(kid_handle *h, kid_grd_chksum *out, int32_t n_out);
 
 /* ---- trajectories: record_posn (FW:5328-5498) as a device pass that appends one record per selected berg
  * to buffers in HBM, and iceberg_trajectories.nc (icebergs_fms2io.F90:1631-2103) written from them: dimension "i", lon,

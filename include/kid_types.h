@@ -236,6 +236,31 @@ typedef struct kid_budget_out {
   double net_heat_to_ocean;    /* IB:3130, since kid_create (KID_S_NET_HEAT_TO_OCEAN) */
 } kid_budget_out;
 
+/* ---- checksums of the gridded fields: checksum_gridded (FW:6685-6758), one record per field in the reference's order:
+ * 13 forcing planes, 35 state planes, 11 static planes.  The names are the reference's labels in upper case. ---- */
+enum {
+  KID_CHK_UO = 0, KID_CHK_VO, KID_CHK_UA, KID_CHK_VA, KID_CHK_UI, KID_CHK_VI, KID_CHK_SSH, KID_CHK_SST, KID_CHK_SSS, KID_CHK_HI, KID_CHK_CN,
+  KID_CHK_CALVING, KID_CHK_CALVING_HFLX,
+  KID_CHK_MASS, KID_CHK_MASS_ON_OCEAN, KID_CHK_AREA_ON_OCEAN, KID_CHK_UVEL_ON_OCEAN, KID_CHK_VVEL_ON_OCEAN, KID_CHK_STORED_ICE,
+  KID_CHK_RMEAN_CALVING, KID_CHK_RMEAN_CALVING_HFLX, KID_CHK_STORED_HEAT, KID_CHK_MELT_B, KID_CHK_MELT_E, KID_CHK_MELT_V,
+  KID_CHK_BERGY_SRC, KID_CHK_BERGY_MELT, KID_CHK_BERGY_MASS, KID_CHK_FL_BITS_SRC, KID_CHK_FL_BITS_MELT, KID_CHK_FL_BITS_MASS,
+  KID_CHK_FL_BERGY_BITS_MASS, KID_CHK_SPREAD_MASS, KID_CHK_SPREAD_AREA, KID_CHK_U_ICEBERG, KID_CHK_V_ICEBERG, KID_CHK_SPREAD_UVEL,
+  KID_CHK_SPREAD_VVEL, KID_CHK_USTAR_ICEBERG, KID_CHK_VAREA, KID_CHK_FLOATING_MELT, KID_CHK_BERG_MELT, KID_CHK_MELT_BY_CLASS,
+  KID_CHK_MELT_B_FL, KID_CHK_MELT_E_FL, KID_CHK_MELT_V_FL, KID_CHK_FL_PARENT_MELT, KID_CHK_FL_CHILD_MELT,
+  KID_CHK_LON, KID_CHK_LAT, KID_CHK_LONC, KID_CHK_LATC, KID_CHK_DX, KID_CHK_DY, KID_CHK_AREA, KID_CHK_MSK, KID_CHK_COS, KID_CHK_SIN,
+  KID_CHK_DEPTH,
+  KID_NCHK = 59
+};
+/* What grd_chksum2 / grd_chksum3 print for one field (FW:6761-6886), over the computational domain: chksum = mpp_chksum of the
+ * field, chksum2 = mpp_chksum of the field times float(i + 2*j) (3-d: + 3*(k-1)), both as the default integers the reference
+ * prints; min, max, mean, rms and the standard deviation about the mean.  present = 0: the handle does not hold the field
+ * (calving never configured, a forcing plane never given) and every other member is zero. */
+typedef struct kid_grd_chksum {
+  int64_t chksum, chksum2;
+  double  minv, maxv, mean, rms, sd;
+  int32_t present, pad_;
+} kid_grd_chksum;
+
 /* diagnostics that the reference guards with `id_*>0` (diag_manager ids, FW:1567-1673) */
 enum {
   KID_DIAG_MELT_BY_CLASS  = 1 << 0,  /* IB:3119 */
