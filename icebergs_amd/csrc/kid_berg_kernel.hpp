@@ -298,21 +298,34 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
     // every lane knows its own cell: the wave walks over the distinct cells of its live lanes (first lane not yet served, its
     // cell by v_readlane, a ballot of the lanes that share it) -- no table look-up, no shuffle
     const unsigned loff = (unsigned)lane * 16u;
-    unsigned long long rem = __ballot(mykey >= 0);
-    int nslot = 0;
+    // The same walk ranks the lanes for the scatter: the lanes of a cell take neighbouring columns of the staging rows (in lane
+    // order), so that seg_flush sums and adds once per distinct cell and plane.  Per run of adjacent lanes (make_runs) an
+    // out-of-place berg was an atomic of its own and split the run it sat in: ~20 runs in a wave at the end of a 16-step
+    // interval against the handful of cells they belong to.
+    const unsigned long long dead = __ballot(mykey < 0);
+    unsigned long long rem = ~dead;
+    int nslot = 0, base = 0;
+    int myhead = 0, mylen = 0, myrank = 0;
     myslot = 0;
     while (rem != 0ull) {  // wave-uniform: one turn per distinct cell
       const int u = (int)__ffsll((long long)rem) - 1;
       const int cu = __builtin_amdgcn_readlane(mykey, u);
       const bool mine = mykey == cu;
-      if (mine) myslot = nslot;
+      const unsigned long long bm = __ballot(mine);
+      const int cnt = __popcll(bm);
+      if (mine) { myslot = nslot; myhead = base; mylen = cnt; myrank = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u)); }
       if (nslot < SLOTS && lane < 34)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gp + (size_t)cu * (size_t)(PK_GSTRIDE * 8) + loff),
                                          (__attribute__((address_space(3))) void *)(wpk + nslot * PK_STRIDE), 16, 0, 0);
-      rem &= ~__ballot(mine);
+      rem &= ~bm;
+      base += cnt;
       ++nslot;
     }
-    seg = make_runs(mykey, (lds_double *)lds_vals, (lds_int *)lds_ints, CHUNK);
+    // (lanes without a cell: the columns behind the last cell's; they only ever stage zeros)
+    if (mykey < 0) myrank = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(dead >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)dead, 0u));
+    // the run tables, one entry per distinct cell; a cell beyond the slots adds nothing (its lanes go to the general build below)
+    seg = seg_tables((lds_double *)lds_vals, (lds_int *)lds_ints, CHUNK);
+    seg_by_cell(seg, mykey >= 0 && myrank == myhead, myslot, myhead, mylen, myslot < SLOTS ? mykey : -1, nslot, myrank);
     // more distinct cells than slots: the lanes of the cells beyond go to the general build one by one (handing over the whole
     // wave made 15 % of the population take the slow path by the end of a 16-step interval)
     if (myslot >= SLOTS) {

@@ -18,8 +18,9 @@ namespace kid {
 // issued per berg and value; LDS ds_add_f64 into a workgroup window was no better (0.53 ms, same-address
 // serialisation).  What is cheap is to let each wave sum its own runs of equal cells first:
 //   * make_runs(): one ballot finds the runs of equal cell index among the 64 lanes (the SoA is cell-sorted, so a
-//     wave holds ~5 runs; unsorted input degrades to 64 runs of one, still correct);
-//   * cell_add() only parks a value in the wave's LDS staging slot [slot][lane];
+//     wave holds ~5 runs; unsorted input degrades to 64 runs of one, still correct) -- the general build; the hot build
+//     groups its lanes by DISTINCT cell instead (seg_by_cell), however the row order has decayed since the last re-binning;
+//   * cell_add() only parks a value in the wave's LDS staging slot [slot][column] (Seg::rank: the lane, or its place in its cell's group);
 //   * seg_flush(): the (slot, run) pairs are dealt to the lanes, each lane sums its run's staged values in lane
 //     order (a fixed order: bitwise reproducible within a wave) and issues ONE atomic for the run.
 // That is ~14x fewer atomics and, unlike a shuffle scan, costs about one LDS write + one LDS read per value.
@@ -41,10 +42,10 @@ struct Seg {
   lds_int *len;      // [64] length of run r
   lds_int *cell;     // [64] cell index of run r (<0: inactive lanes, nothing to add)
   lds_int *plane;    // [KID_CHUNK] plane id of staged slot
-  unsigned long long heads;  // bit l: lane l starts a run
   int R;             // number of runs in this wave
   int npend;         // staged slots (wave-uniform)
   int chunk;         // staged slots per flush (KID_CHUNK; fewer in the builds that trade staging rows for a third wave per SIMD)
+  int rank;          // this lane's column of a staging row (make_runs: the lane number; hot build: seg_by_cell below)
   static constexpr bool stage = false;
 };
 // LDS a workgroup of `waves` waves needs for its Seg tables
@@ -56,17 +57,33 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
   return v;
 }
-__device__ __forceinline__ Seg make_runs(int key, lds_double *vals, lds_int *ints, int chunk = KID_CHUNK) {
+// this wave's staging block and tables, nothing staged, no runs yet
+__device__ __forceinline__ Seg seg_tables(lds_double *vals, lds_int *ints, int chunk = KID_CHUNK) {
   Seg s;
-  const int lane = (int)__lane_id(), wave = (int)(threadIdx.x >> 6);
+  const int wave = (int)(threadIdx.x >> 6);
   s.chunk = chunk;
   s.val = vals + wave * (chunk * KID_ROW);
   lds_int *base = ints + wave * (3 * 64 + chunk);
   s.head = base; s.len = base + 64; s.cell = base + 128; s.plane = base + 192;
+  s.R = 0; s.npend = 0; s.rank = (int)__lane_id();
+  return s;
+}
+// The hot build's scatter: one "run" per DISTINCT cell of the wave instead of one per run of adjacent lanes.  Its walk over the
+// distinct cells (kid_berg_kernel.hpp) gives every lane a column of the staging rows -- the lanes of a cell side by side in
+// lane order, cell after cell in the order of the walk, the lanes without a cell behind the last one -- and calls this once
+// per wave with what each lane learned in its cell's turn: `first` (it is the lowest lane of its cell), the cell's first
+// column and lane count, and the cell (-1: nothing to add).  seg_flush_impl reads the tables exactly as make_runs leaves them.
+__device__ __forceinline__ void seg_by_cell(Seg &s, bool first, int slot, int head, int len, int cell, int ncells, int rank) {
+  if (first) { s.head[slot] = head; s.len[slot] = len; s.cell[slot] = cell; }
+  s.R = ncells; s.rank = rank;
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ Seg make_runs(int key, lds_double *vals, lds_int *ints, int chunk = KID_CHUNK) {
+  Seg s = seg_tables(vals, ints, chunk);
+  const int lane = (int)__lane_id();
   const int prev = __shfl_up(key, 1);
   const bool is_head = (lane == 0) || (prev != key);
   const unsigned long long heads = __ballot(is_head);
-  s.heads = heads;
   s.R = __popcll(heads);
   if (is_head) {
     const int r = __popcll(heads & ((1ull << lane) - 1ull));
@@ -139,7 +156,7 @@ __device__ __forceinline__ void cell_add(double *acc, size_t ncell, int plane, i
   if (active && v == 1.2345e-300) acc[(size_t)plane * ncell + c] = v;
   return;
 #endif
-  s.val[s.npend * KID_ROW + (int)__lane_id()] = active ? v : 0.0;
+  s.val[s.npend * KID_ROW + s.rank] = active ? v : 0.0;
   s.plane[s.npend] = plane;
   s.npend += 1;
   if (s.npend == s.chunk) seg_flush(s, acc, ncell);
