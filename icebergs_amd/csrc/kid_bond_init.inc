@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) bond_count_kernel(const DevGrid g, const 
 static int bond_extents(kid_handle *h, double ext[2]) {
   if (h->bond_ext_valid) { ext[0] = h->bond_ext[0]; ext[1] = h->bond_ext[1]; return KID_OK; }
   ext[0] = ext[1] = 0.;
-  if (h->have_static) {
+  if (h->forc.have_static) {
     const size_t nc = h->ncell;
     const int ni = h->ni, nj = h->nj;
     std::vector<double> dx(nc), dy(nc), lon(nc), lat(nc);

@@ -338,8 +338,8 @@ int kid_calving(kid_handle *h, const kid_calving_in *in, double *scalars) {
   if (!h || !in || !in->calving || !in->calving_hflx) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_calving"); if (rc_h) return rc_h; }
   if (!h->calving_on) { h->err = "kid_set_calving_params must be called first"; return KID_EINVAL; }
-  if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
-  if (!h->params.old_interp_flds_order && !h->have_forcing) { h->err = "new bergs interpolate the forcing (IB:6353): set it before kid_calving"; return KID_EINVAL; }
+  if (need_static(h)) return KID_EINVAL;
+  if (!h->params.old_interp_flds_order && !h->forc.have_forcing) { h->err = "new bergs interpolate the forcing (IB:6353): set it before kid_calving"; return KID_EINVAL; }
   { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }   // new rows must start in the hot lane
   { const int rc = refresh_tables(h); if (rc) return rc; }
   const kid_grid_desc &d = h->gd;

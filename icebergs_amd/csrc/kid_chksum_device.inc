@@ -423,7 +423,7 @@ extern "C" int kid_checksum_gridded(kid_handle *h, kid_grd_chksum *out, int32_t 
   // forcing: the planes kid_get_forcing returns, each once it has been given; grd%calving, grd%calving_hflx: kid_get_calving
   static const int forc[11][2] = {{KID_CHK_UO, KID_F_UO}, {KID_CHK_VO, KID_F_VO}, {KID_CHK_UA, KID_F_UA}, {KID_CHK_VA, KID_F_VA}, {KID_CHK_UI, KID_F_UI}, {KID_CHK_VI, KID_F_VI},
                                   {KID_CHK_SSH, KID_F_SSH}, {KID_CHK_SST, KID_F_SST}, {KID_CHK_SSS, KID_F_SSS}, {KID_CHK_HI, KID_F_HI}, {KID_CHK_CN, KID_F_CN}};
-  for (const auto &m : forc) set(m[0], h->d_forcing[m[1]], 1, h->forcing_held[m[1]]);
+  for (const auto &m : forc) set(m[0], h->d_forcing[m[1]], 1, forcing_held(h, m[1]));
   const bool calv = h->calving_on && h->d_calv_state;
   set(KID_CHK_CALVING, calv ? calv_plane(h, CALV_CALVING) : nullptr, 1, calv);
   set(KID_CHK_CALVING_HFLX, calv ? calv_plane(h, CALV_HFLX) : nullptr, 1, calv);
@@ -431,15 +431,14 @@ extern "C" int kid_checksum_gridded(kid_handle *h, kid_grd_chksum *out, int32_t 
   set(KID_CHK_RMEAN_CALVING, calv ? calv_plane(h, CALV_RMEAN) : nullptr, 1, calv);
   set(KID_CHK_RMEAN_CALVING_HFLX, calv ? calv_plane(h, CALV_RMEAN_HFLX) : nullptr, 1, calv);
   set(KID_CHK_STORED_HEAT, calv ? calv_plane(h, CALV_STORED_HEAT) : nullptr, 1, calv);
-  // state: the accumulator planes of kid_get_accumulators; a plane the step neither zeroes nor fills (nacc_active, footprint_needed) reads as zeros
-  const int nacc = nacc_active(h);
-  const bool foot = footprint_needed(h->params);
+  // state: the accumulator planes of kid_get_accumulators; a plane the step neither zeroes nor fills (plane_range_live, kid_planes.hpp) reads as zeros
   auto acc = [&](int which, int plane, int nk) {
-    const bool live = plane + nk <= nacc && (foot || plane < KID_A_AREA_ON_OCEAN || plane >= KID_NACC_CORE);
+    const bool live = plane_range_live(plane, nk, h->params.pass_fields_to_ocean_model, h->params.diag_mask);
     tab.f[which] = ChkField{live ? h->d_acc + (size_t)plane * h->ncell : nullptr, nk, 1};
   };
-  static const int accs[][3] = {{KID_CHK_MASS, KID_A_MASS, 1}, {KID_CHK_MASS_ON_OCEAN, KID_A_MASS_ON_OCEAN, 9}, {KID_CHK_AREA_ON_OCEAN, KID_A_AREA_ON_OCEAN, 9},
-    {KID_CHK_UVEL_ON_OCEAN, KID_A_UVEL_ON_OCEAN, 9}, {KID_CHK_VVEL_ON_OCEAN, KID_A_VVEL_ON_OCEAN, 9}, {KID_CHK_MELT_B, KID_A_MELT_BUOY, 1}, {KID_CHK_MELT_E, KID_A_MELT_EROS, 1},
+  constexpr int S = ON_OCEAN_SLOTS;
+  static const int accs[][3] = {{KID_CHK_MASS, KID_A_MASS, 1}, {KID_CHK_MASS_ON_OCEAN, KID_A_MASS_ON_OCEAN, S}, {KID_CHK_AREA_ON_OCEAN, KID_A_AREA_ON_OCEAN, S},
+    {KID_CHK_UVEL_ON_OCEAN, KID_A_UVEL_ON_OCEAN, S}, {KID_CHK_VVEL_ON_OCEAN, KID_A_VVEL_ON_OCEAN, S}, {KID_CHK_MELT_B, KID_A_MELT_BUOY, 1}, {KID_CHK_MELT_E, KID_A_MELT_EROS, 1},
     {KID_CHK_MELT_V, KID_A_MELT_CONV, 1}, {KID_CHK_BERGY_SRC, KID_A_BERGY_SRC, 1}, {KID_CHK_BERGY_MELT, KID_A_BERGY_MELT, 1}, {KID_CHK_BERGY_MASS, KID_A_BERGY_MASS, 1},
     {KID_CHK_FL_BITS_SRC, KID_A_FL_BITS_SRC, 1}, {KID_CHK_FL_BITS_MELT, KID_A_FL_BITS_MELT, 1}, {KID_CHK_FL_BITS_MASS, KID_A_FL_BITS_MASS, 1},
     {KID_CHK_FL_BERGY_BITS_MASS, KID_A_FL_BERGY_BITS_MASS, 1}, {KID_CHK_U_ICEBERG, KID_A_U_ICEBERG, 1}, {KID_CHK_V_ICEBERG, KID_A_V_ICEBERG, 1}, {KID_CHK_VAREA, KID_A_VIRTUAL_AREA, 1},
@@ -451,6 +450,6 @@ extern "C" int kid_checksum_gridded(kid_handle *h, kid_grd_chksum *out, int32_t 
                                  {KID_CHK_SPREAD_VVEL, KID_O_SPREAD_VVEL}, {KID_CHK_USTAR_ICEBERG, KID_O_USTAR_ICEBERG}};
   for (const auto &m : outs) set(m[0], h->d_out + (size_t)m[1] * h->ncell, 1, true);
   // static: the planes of kid_set_static_grid, in the enum's order (lonc and latc are optional there)
-  for (int k = 0; k < KID_NGRID_STATIC; ++k) set(KID_CHK_LON + k, h->d_static[k], 1, h->have_static && ((k != KID_G_LONC && k != KID_G_LATC) || h->have_centres));
+  for (int k = 0; k < KID_NGRID_STATIC; ++k) set(KID_CHK_LON + k, h->d_static[k], 1, h->forc.have_static && ((k != KID_G_LONC && k != KID_G_LATC) || h->forc.have_centres));
   return chkd_planes(h, tab, KID_NCHK, out);
 }

@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256) halo_fold_kernel(double *__restrict__ pla
 }
 }  // namespace
 
-static int halo_planes(const kid_handle *h) { return footprint_needed(h->params) ? 36 : 9; }
+static int halo_planes(const kid_handle *h) { return kid::halo_plane_count(h->params.pass_fields_to_ocean_model, h->params.diag_mask); }
 // the strips of one call; false: axis or width out of range
 static bool halo_strips(const kid_handle *h, int axis, int w, bool pack, HaloStrips &s) {
   const kid_grid_desc &d = h->gd;
@@ -84,7 +84,7 @@ template <bool PACK>
 static int halo_launch(kid_handle *h, const HaloStrips &s) {
   const long long total = 2ll * s.np * s.nrow * s.ncol;
   hipLaunchKernelGGL(halo_strips_kernel<PACK>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
-                     h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, h->ncell, s);
+                     on_ocean_base(h), h->ncell, s);
   KID_HIP(h, hipGetLastError());
   return KID_OK;
 }
@@ -100,7 +100,7 @@ template <bool SELF>
 static int fold_launch(kid_handle *h, const FoldStrip &f) {
   const long long total = (long long)f.np * f.w * f.ncol;
   hipLaunchKernelGGL(halo_fold_kernel<SELF>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
-                     h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, h->ncell, f);
+                     on_ocean_base(h), h->ncell, f);
   KID_HIP(h, hipGetLastError());
   return KID_OK;
 }
@@ -111,8 +111,8 @@ int kid_calculate_mass_on_ocean(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_calculate_mass_on_ocean"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));  // IB:4984-4987
-  return launch_berg<PH_SPREAD>(h);
+  const int rc = zero_planes(h, ON_OCEAN_ALL);   // IB:4984-4987
+  return rc ? rc : launch_berg<PH_SPREAD>(h);
 }
 
 int kid_halo_plane_count(kid_handle *h, int32_t *nplanes) {

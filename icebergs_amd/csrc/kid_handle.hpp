@@ -38,6 +38,17 @@ enum { KID_PERM_MAX = KID_NB_F64 + KID_NB_I32 + 2 };   // every field, the ids, 
 struct PermTable { const void *src[KID_PERM_MAX]; void *dst[KID_PERM_MAX]; int n8, n4; };
 }  // namespace
 
+// one set of what pack_forcing builds (kid_cells.inc): the per-cell records, the gathered cell packets of the hot build, and
+// the device copy of the grid descriptor that points at them (berg_kernel reads it as a table)
+struct ForcingSet { VelRec *vel = nullptr; TrcRec *trc = nullptr; double *pkt = nullptr; DevGrid *d_grid = nullptr; };
+// what the handle has been given of the grid and the forcing
+struct ForcingState {
+  bool have_static = false, have_forcing = false;
+  bool have_centres = false;   // kid_set_static_grid was given lonc and latc (optional there; the cell search walks on them)
+  bool have_planes = false;    // d_forcing holds all eleven planes
+  bool held[KID_NFORCING] = {};   // d_forcing[k] holds a plane that was given (kid_set_forcing, kid_ingest_forcing; ssh also from kid_set_forcing_device, kid_step_prepare)
+};
+
 struct kid_handle {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -53,7 +64,7 @@ struct kid_handle {
   double auto_growth = 0.; int64_t auto_min_free = 0, auto_max_capacity = 0;
   // device memory
   double *d_static[KID_NGRID_STATIC] = {}, *d_forcing[KID_NFORCING] = {};
-  VelRec *d_vel = nullptr; TrcRec *d_trc = nullptr; GeoRec *d_geo = nullptr; double *d_hotok = nullptr; double *d_latref = nullptr;
+  GeoRec *d_geo = nullptr; double *d_hotok = nullptr; double *d_latref = nullptr;
   // the accumulator block: KID_NSCALAR step scalars, then KID_NACC planes of ncell (scalars first, so that they and the planes a
   // step really fills -- a prefix -- are ONE contiguous range for the all-reduce); d_acc points at plane 0
   double *d_acc_own = nullptr, *d_acc = nullptr;
@@ -62,7 +73,6 @@ struct kid_handle {
   BergPtrs bp{};
   BergPtrs *d_bp = nullptr;      // device copy of the field-pointer table
   kid_params *d_params = nullptr; // device copy of the parameter block
-  DevGrid *d_grid = nullptr;      // device copy of the grid descriptor (berg_kernel reads it as a table)
   bool tables_dirty = true;
   Scratch scan_tmp;             // the scan of the row flags (kid_compact_bergs)
   unsigned long long *d_count = nullptr;
@@ -87,8 +97,9 @@ struct kid_handle {
   // "slow lane" schedule (kid_set_side_stream mode 2, launch_berg_lanes in kid_launch.inc)
   int side_mode = 0; int *d_lane = nullptr, *d_lane_alt = nullptr; hipEvent_t evR = nullptr; int lane_step = 1; bool lanes_active = false, carry_valid = false, evC_live = false;
   hipEvent_t evC = nullptr, evP = nullptr;
-  VelRec *d_vel2 = nullptr; TrcRec *d_trc2 = nullptr; DevGrid *d_grid2 = nullptr; int forc_parity = 0;  // forcing records of the odd steps
-  double *d_pkt[2] = {nullptr, nullptr};   // gathered cell packets of the hot build, one set per parity of the forcing records
+  // The forcing records, twice: while a side stream is in use, general-build launches of the previous step may still read
+  // theirs, so pack_forcing (kid_cells.inc) alternates between the two sets and nothing else changes forc_parity.
+  ForcingSet fset[2]; int forc_parity = 0;
   // A/B switches for measurements and tests, read from the environment ONCE, when the handle is created (nothing on the
   // stepping path calls getenv): KID_MTS_NO_GRAPH, KID_STABLE_RESORT, KID_NO_PLAIN_BUILD, KID_FL_UNFUSED, KID_NEW_ORDER_UNFUSED,
   // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_CHKSUM_TIMING (kid_bergs_chksum_device prints the times of its parts), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
@@ -139,9 +150,7 @@ struct kid_handle {
   double *d_btraj_f[16] = {}; int64_t *d_btraj_id[2] = {}; int32_t *d_btraj_i[2] = {}; long long btraj_capacity = 0, btraj_count_bound = 0;   // bond samples
   double *d_spread_mass_old = nullptr;   // grd%spread_mass_old (find_melt_using_spread_mass, IB:5495-5497) + spread_mass_tmp; the handle's own or the caller's (kid_bind_spread_mass_old)
   double *d_spread_mass_old_own = nullptr;
-  bool have_static = false, have_forcing = false, have_planes = false;  // have_planes: d_forcing holds all eleven planes
-  bool forcing_held[KID_NFORCING] = {};   // d_forcing[k] holds a plane that was given (kid_set_forcing, kid_ingest_forcing; ssh also from kid_set_forcing_device)
-  bool have_centres = false;   // kid_set_static_grid was given lonc and latc (optional there; the cell search walks on them)
+  ForcingState forc;           // written by kid_set_static_grid and forcing_given (kid_cells.inc)
   int restart_locate = 0;      // kid_set_restart_locate: 0 kid_read_restart trusts the file's ine, jne; 1, 2 it searches (kid_locate.inc)
   double *d_calv_state = nullptr, *d_calv_scal = nullptr, *d_calv_part = nullptr; unsigned char *d_calv_flag = nullptr; int2 *d_calv_list = nullptr; double *calv_host = nullptr; kid_calving_params calv_params{};  // kid_calving (kid_calving.inc)
   bool calving_on = false, calving_first_call = true, rmean_init = false, rmean_hflx_init = false;
@@ -171,7 +180,7 @@ struct kid_handle {
 
 // host-side functions used before the file that defines them (the .inc files are included where their kernels belong)
 extern "C" {
-static int refresh_tables(kid_handle *h);
+static int refresh_tables(kid_handle *h), join_side(kid_handle *h);
 static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one)
 static int rebin_plan(kid_handle *h, bool dead_last);
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count), rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);

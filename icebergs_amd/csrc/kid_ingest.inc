@@ -156,7 +156,7 @@ static int ingest_stage(kid_handle *h, const kid_forcing_in *in, const size_t cn
 
 int kid_ingest_forcing(kid_handle *h, const kid_forcing_in *in) {
   if (!h || !in) return KID_EINVAL;
-  if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
+  if (need_static(h)) return KID_EINVAL;
   const kid_grid_desc &d = h->gd;
   const int nic = d.iec - d.isc + 1, njc = d.jec - d.jsc + 1;
   if (d.isc - 1 < d.isd || d.iec + 1 > d.ied || d.jsc - 1 < d.jsd || d.jec + 1 > d.jed) { h->err = "forcing ingest needs a halo of at least one cell"; return KID_EINVAL; }
@@ -214,18 +214,12 @@ int kid_ingest_forcing(kid_handle *h, const kid_forcing_in *in) {
   }
   hipLaunchKernelGGL(ingest_scrub_kernel, dim3(nb), dim3(256), 0, h->stream, a);
   KID_HIP(h, hipGetLastError());
-  h->have_forcing = true; h->have_planes = true;
-  for (int k = 0; k < KID_NFORCING; ++k) h->forcing_held[k] = true;
-  const double *none[KID_NFORCING] = {};
-  const int rc = pack_forcing(h, none);  // the per-cell records the berg kernels read
-  if (rc) return rc;
-  if (!in->on_device) KID_HIP(h, hipStreamSynchronize(h->stream));  // the host arrays may be reused by the caller
-  return KID_OK;
+  return forcing_given(h, (1u << KID_NFORCING) - 1u, nullptr, !in->on_device);  // every plane; the per-cell records the berg kernels read
 }
 
 int kid_get_forcing(kid_handle *h, double *const fields[KID_NFORCING]) {
   if (!h || !fields) return KID_EINVAL;
-  if (!h->have_planes) { h->err = "the handle holds no forcing planes (kid_set_forcing with all fields, or kid_ingest_forcing)"; return KID_EINVAL; }
+  if (!h->forc.have_planes) { h->err = "the handle holds no forcing planes (kid_set_forcing with all fields, or kid_ingest_forcing)"; return KID_EINVAL; }
   KID_HIP(h, hipSetDevice(h->device));
   for (int k = 0; k < KID_NFORCING; ++k)
     if (fields[k]) KID_HIP(h, hipMemcpyAsync(fields[k], h->d_forcing[k], h->ncell * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -35,7 +35,7 @@ static bool lanes_eligible(const kid_handle *h) {
 // -------------------------------------------------------------------------------------------------------
 // what every launch of one launch_berg / launch_berg_lanes call shares
 struct BergLaunch { const DevGrid *gtab; bool plain, flprof; };
-static BergLaunch berg_launch(const kid_handle *h) { return {h->forc_parity ? h->d_grid2 : h->d_grid, plain_namelist(h), fl_profile_namelist(h)}; }
+static BergLaunch berg_launch(const kid_handle *h) { return {h->fset[h->forc_parity].d_grid, plain_namelist(h), fl_profile_namelist(h)}; }
 
 template <bool RK, bool OLD, unsigned PH, bool FAST, int K, bool STAGE>
 static int launch_instance(kid_handle *h, const BergLaunch &c, hipStream_t s, unsigned nblocks, const Redo &redo) {
@@ -172,7 +172,7 @@ static int launch_berg_part(kid_handle *h, const BergLaunch &c, bool stage, cons
 // One phase mask over the rows [range_k0, range_k0 + range_len) (default: all)
 template <unsigned PH>
 static int launch_phase(kid_handle *h, long long range_k0 = 0, long long range_len = -1) {
-  if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
+  if (need_forcing(h)) return KID_EINVAL;
   if (h->n == 0 || range_len == 0) return KID_OK;
   const bool old = h->params.old_interp_flds_order != 0, whole = range_k0 == 0 && range_len < 0;
   if (!old && !(PH & PH_INTERP) && (PH & (PH_EVOLVE | PH_THERMO)) && !h->flags.store_env) {
@@ -232,7 +232,7 @@ template <bool OLDV>
 static int launch_berg_lanes(kid_handle *h) {
   constexpr unsigned PH = OLDV ? PH_STEP : (PH_INTERP | PH_STEP);
   static_assert(instance_exists(OLDV, PH, false), "the fused step of this order");
-  if (!h->have_forcing) { h->err = "kid_set_forcing must be called before stepping"; return KID_EINVAL; }
+  if (need_forcing(h)) return KID_EINVAL;
   { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (this schedule re-bins inside the step, with the copy)
   { int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
   const BergLaunch c = berg_launch(h);
@@ -293,14 +293,6 @@ static int launch_berg_lanes(kid_handle *h) {
 static int launch_fused_step(kid_handle *h) {
   if (!lanes_eligible(h)) return launch_ordered<PH_STEP>(h);
   return h->params.old_interp_flds_order ? launch_berg_lanes<true>(h) : launch_berg_lanes<false>(h);
-}
-// the 'mass' gather of the on-ocean planes into a plane of spread_mass_old, and the planes reset (IB:5495-5497, IB:3411-3413)
-static int gather_mass_and_reset(kid_handle *h, double *dst) {
-  const int ncomp = (h->gd.iec - h->gd.isc + 1) * (h->gd.jec - h->gd.jsc + 1);
-  hipLaunchKernelGGL(mass_gather_kernel, dim3((unsigned)((ncomp + 255) / 256)), dim3(256), 0, h->stream, dev_grid(h), (const double *)h->d_acc, dst, h->ncell,
-                     h->params.periodic_reentry != 0 && h->gd.Lx > 0.);
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));
-  return KID_OK;
 }
 
 // -------------------------------------------------------------------------------------------------------
@@ -370,7 +362,8 @@ static int step_spread_mass(kid_handle *h) {
   }
   int rc = KID_OK;
   if (!p.static_icebergs) { rc = p.old_interp_flds_order ? launch_berg<PH_EVOLVE>(h) : launch_berg<PH_INTERP | PH_EVOLVE>(h); if (rc) return rc; }
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));
+  rc = zero_planes(h, ON_OCEAN_ALL);
+  if (rc) return rc;
   const Flags keep = h->flags;
   h->flags.no_diag = 1; h->flags.footprint = 0;
   rc = launch_berg<PH_SPREAD>(h);
@@ -425,18 +418,16 @@ int kid_thermodynamics(kid_handle *h) {
     h->err = "find_melt_using_spread_mass: the phase entry points do not gather spread_mass_old (IB:5490-5503); use kid_run_step / kid_step_local";
     return KID_EUNSUPPORTED;
   }
-  // IB:2872-2873
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_UVEL_ON_OCEAN * h->ncell, 0, 18 * h->ncell * sizeof(double), h->stream));
-  return launch_berg<PH_THERMO>(h);
+  const int rc = zero_planes(h, ON_OCEAN_VEL);   // IB:2872-2873
+  return rc ? rc : launch_berg<PH_THERMO>(h);
 }
 int kid_create_gridded_icebergs_fields(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_create_gridded_icebergs_fields"); if (rc_h) return rc_h; }
   KID_HIP(h, hipSetDevice(h->device));
-  KID_HIP(h, hipMemsetAsync(h->d_acc + (size_t)KID_A_MASS_ON_OCEAN * h->ncell, 0, 36 * h->ncell * sizeof(double), h->stream));  // IB:4984-4987
-  int rc = launch_berg<PH_SPREAD>(h);
-  if (rc) return rc;
-  return launch_gather(h);
+  int rc = zero_planes(h, ON_OCEAN_ALL);   // IB:4984-4987
+  if (!rc) rc = launch_berg<PH_SPREAD>(h);
+  return rc ? rc : launch_gather(h);
 }
 
 int kid_step_local(kid_handle *h) {   // IB:5409-5512

@@ -180,8 +180,8 @@ extern "C" {
 
 // what the search needs of the grid: the cell centres and one halo cell around the computational domain
 static int locate_check(kid_handle *h, const char *what) {
-  if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
-  if (!h->have_centres) { h->err = std::string(what) + ": the static grid was set without lonc / latc, which the search walks on"; return KID_EINVAL; }
+  if (need_static(h)) return KID_EINVAL;
+  if (!h->forc.have_centres) { h->err = std::string(what) + ": the static grid was set without lonc / latc, which the search walks on"; return KID_EINVAL; }
   const kid_grid_desc &d = h->gd;
   // (on a domain one cell wide the inset corners isc+1, iec-1 are themselves outside it, and the first move looks one cell further)
   const int w = (d.iec - d.isc < 1 || d.jec - d.jsc < 1) ? 2 : 1;

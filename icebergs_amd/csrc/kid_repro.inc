@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(256) repro_fold_kernel(const FoldTab ft, const
   }
   if (b == e) return;
   const int v = G.kind - 1;
-  const int base = KID_A_MASS_ON_OCEAN + 9 * v;
+  const int base = on_ocean_family(v).first;
   double a[9];
 #pragma unroll
   for (int s = 0; s < 9; ++s) a[s] = acc[(size_t)(base + s) * ncell + c];
@@ -232,13 +232,12 @@ static int repro_fold(kid_handle *h, bool thermo, bool spread, long long k0, lon
     FoldGroup &G = ft.g[ft.ng - 1];
     G.plane[G.n++] = plane;
   };
-  const int nacc = nacc_active(h);
   if (thermo) add_value(-1);
-  for (int pl = 0; pl < nacc; ++pl)
-    if (pl < KID_A_MASS_ON_OCEAN || pl >= KID_NACC_CORE) add_value(pl);
+  for (int pl = 0; pl < KID_NACC; ++pl)   // (the on-ocean families are folded as groups of nine, below)
+    if (!ON_OCEAN_ALL.contains(pl) && plane_range_live(pl, 1, h->params.pass_fields_to_ocean_model, h->params.diag_mask)) add_value(pl);
   if (spread) {
-    ft.g[ft.ng].kind = 1; ft.g[ft.ng].n = 9; ++ft.ng;
-    if (h->flags.footprint) for (int v = 1; v < 4; ++v) { ft.g[ft.ng].kind = 1 + v; ft.g[ft.ng].n = 9; ++ft.ng; }
+    ft.g[ft.ng].kind = 1; ft.g[ft.ng].n = ON_OCEAN_SLOTS; ++ft.ng;
+    if (h->flags.footprint) for (int v = 1; v < 4; ++v) { ft.g[ft.ng].kind = 1 + v; ft.g[ft.ng].n = ON_OCEAN_SLOTS; ++ft.ng; }
   }
   const long long nt = (long long)ft.ng * (long long)h->ncell;
   hipLaunchKernelGGL(repro_fold_kernel, dim3((unsigned)((nt + 255) / 256)), block, 0, h->stream, ft, (const int *)h->rp.rows[1], (const int *)h->rp.cs,

@@ -508,7 +508,7 @@ int kid_write_restart(kid_handle *h, const char *dir) {
 // With kid_set_restart_locate (ignore_ij_restart) the cells come from the positions instead (kid_locate.inc); the rest is the same.
 int kid_read_restart(kid_handle *h, const char *dir) {
   if (!h || !dir) return KID_EINVAL;
-  if (!h->have_static) { h->err = "kid_set_static_grid must be called first"; return KID_EINVAL; }
+  if (need_static(h)) return KID_EINVAL;
   KID_HIP(h, hipSetDevice(h->device));
   { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }
   const std::string base(dir), path = base + "/icebergs.res.nc";

@@ -337,7 +337,7 @@ int kid_compact_bergs(kid_handle *h) {
 // emigrants right after the re-binning.
 static bool rebin_fusable(const kid_handle *h) {
   const kid_params &p = h->params;
-  return !h->dbg.rebin_eager && !h->repro && !h->mig_mode && !h->pipelined && h->have_forcing && p.Runge_not_Verlet && p.old_interp_flds_order &&
+  return !h->dbg.rebin_eager && !h->repro && !h->mig_mode && !h->pipelined && h->forc.have_forcing && p.Runge_not_Verlet && p.old_interp_flds_order &&
          !p.static_icebergs && !p.mts && !p.interactive_icebergs_on && !p.footloose && !p.find_melt_using_spread_mass && !lanes_eligible(h) && plain_namelist(h);
 }
 int kid_move_berg_between_cells(kid_handle *h) {
