@@ -33,6 +33,13 @@ __device__ __forceinline__ int32_t ldg(const int32_t *q, long long k) { return *
 // by the compiler, behind the wait for `alive` -- a second round trip to HBM per wave.  The dead path "uses" them too.
 __device__ __forceinline__ void keep(double x) { asm volatile("" ::"v"(x)); }
 __device__ __forceinline__ void keep(int32_t x) { asm volatile("" ::"v"(x)); }
+// Field f of row k -- or 0. where the launch knows the field as zeros (z: wave-uniform, from a kernel argument).  The load is
+// still issued, on the line of xi that the same batch fetches anyway: the head of the kernel stays one batch of loads behind one
+// wait (a branch around a load there made the join wait), and nothing comes from HBM for it.
+template <class B> __device__ __forceinline__ double ldg_or_zero(bool z, const B &b, int f, long long k) {
+  const double v = ldg(z ? b.f[KID_B_XI] : b.f[f], k);
+  return z ? 0. : v;
+}
 __device__ __forceinline__ void stg(double *q, long long k, double v) { *(gdouble *)((gchar *)q + (size_t)((unsigned)k << 3)) = v; }
 __device__ __forceinline__ void stg(int32_t *q, long long k, int32_t v) { *(gint32 *)((gchar *)q + (size_t)((unsigned)k << 2)) = v; }
 // the plain builds (K = 1 and, with store_env on, K = 3; kid_device.hpp) are launched only with the other four flags zero; the footloose profile (K = 2) with no static
@@ -83,7 +90,10 @@ struct RebinTab { BergPtrs dst; const void *xs[KID_RB_NX8 + KID_RB_NX4]; void *x
 struct Redo { int *list; int *count; long long k0, klen; int *lane; int step;    // k0, klen: the rows the hot build covers in this launch
               int *fl_cursor; int32_t *fl_counter; long long fl_capacity; int fl_iNg; unsigned fl_step;   // PH_FL: where footloose children go (FlChildCtx)
               StageTab st{};
-              const RebinTab *rb = nullptr; const unsigned *perm = nullptr; };   // REBIN: destination table + extras, source row of every destination row
+              const RebinTab *rb = nullptr; const unsigned *perm = nullptr;      // REBIN: destination table + extras, source row of every destination row
+              // plain hot builds (K = 1, 3): the fp64 fields that hold zeros in every row (a bit per field; kid_rows_plan.hpp,
+              // launch_hot): neither loaded nor stored.  0 for every other build
+              unsigned long long zero = 0ull; };
 // the fields a plain hot build stores for a berg it steps: by the evolve, by the thermodynamics (K = 3: with the environment)
 constexpr unsigned long long rb_bit(int f) { return 1ull << f; }
 constexpr unsigned long long KID_RB_DYN = rb_bit(KID_B_LON) | rb_bit(KID_B_LAT) | rb_bit(KID_B_UVEL) | rb_bit(KID_B_VVEL) | rb_bit(KID_B_AXN) | rb_bit(KID_B_AYN) |
@@ -192,6 +202,13 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   if constexpr (STAGE) { if (inrange) redo.st.key[k] = -1; }   // (rewritten below by a row that contributes)
   // REBIN: kk is the destination row, ks the row it comes from; otherwise they are the same row
   long long ks = kk;
+  // what this launch need not move (Redo::zero).  REBIN: a field of these that the permutation does move gets its zeros stored
+  constexpr bool ZSKIP = FAST && (K == 1 || K == 3);
+  const unsigned long long zmask = ZSKIP ? redo.zero : 0ull;
+  const bool z_axn = (zmask & rb_bit(KID_B_AXN)) != 0ull, z_ayn = (zmask & rb_bit(KID_B_AYN)) != 0ull;
+  const bool z_bits = (zmask & rb_bit(KID_B_MASS_OF_BITS)) != 0ull, z_hd = (zmask & rb_bit(KID_B_HEAT_DENSITY)) != 0ull;
+  [[maybe_unused]] unsigned long long rb_moved = 0ull;
+  if constexpr (REBIN) rb_moved = ((cRebinTab *)redo.rb)->moved;
   [[maybe_unused]] double x8[KID_RB_NX8];
   [[maybe_unused]] int32_t x4[KID_RB_NX4];
   if constexpr (REBIN) {
@@ -216,7 +233,7 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   d.uvel_prev = 0.; d.vvel_prev = 0.;
   d.axn = 0.; d.ayn = 0.; d.bxn = 0.; d.byn = 0.;
   if (PH & PH_EVOLVE) {
-    d.axn = ldg(b.f[KID_B_AXN], ks); d.ayn = ldg(b.f[KID_B_AYN], ks);
+    d.axn = ldg_or_zero(z_axn, b, KID_B_AXN, ks); d.ayn = ldg_or_zero(z_ayn, b, KID_B_AYN, ks);
     if (!RK) { d.bxn = ldg(b.f[KID_B_BXN], ks); d.byn = ldg(b.f[KID_B_BYN], ks); }
   }
   BergThermo t;
@@ -234,8 +251,8 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
   static_assert(!REBIN || PARK, "the re-binning instance reads its row at the head of the kernel only (ks); the loads further down use kk");
   double park_ms = 0., park_bits = 0., park_hd = 0., park_flk = 0., park_flbits = 0., park_flbergy = 0.;
   if constexpr (PARK) {
-    park_ms = ldg(b.f[KID_B_MASS_SCALING], ks); park_bits = ldg(b.f[KID_B_MASS_OF_BITS], ks);
-    park_hd = (PH & PH_THERMO) ? ldg(b.f[KID_B_HEAT_DENSITY], ks) : 0.;
+    park_ms = ldg(b.f[KID_B_MASS_SCALING], ks); park_bits = ldg_or_zero(z_bits, b, KID_B_MASS_OF_BITS, ks);
+    park_hd = (PH & PH_THERMO) ? ldg_or_zero(z_hd, b, KID_B_HEAT_DENSITY, ks) : 0.;
     if (Fl<K>::has_fl(fl)) {
       park_flk = ldg(b.f[KID_B_FL_K], ks); park_flbits = ldg(b.f[KID_B_MASS_OF_FL_BITS], ks); park_flbergy = ldg(b.f[KID_B_MASS_OF_FL_BERGY_BITS], ks);
     }
@@ -416,8 +433,13 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
           if (!back) t.alive = false;
         }
         stg(bd.f[KID_B_LON], kk, d.lon); stg(bd.f[KID_B_LAT], kk, d.lat); stg(bd.f[KID_B_UVEL], kk, d.uvel); stg(bd.f[KID_B_VVEL], kk, d.vvel);
-        stg(bd.f[KID_B_AXN], kk, d.axn); stg(bd.f[KID_B_AYN], kk, d.ayn); stg(bd.f[KID_B_BXN], kk, d.bxn); stg(bd.f[KID_B_BYN], kk, d.byn);
+        // (axn, ayn known as zeros: the step leaves them +0. -- RK -- and the row holds zeros already)
+        if (!z_axn || (REBIN && (rb_moved & rb_bit(KID_B_AXN)) != 0ull)) stg(bd.f[KID_B_AXN], kk, d.axn);
+        if (!z_ayn || (REBIN && (rb_moved & rb_bit(KID_B_AYN)) != 0ull)) stg(bd.f[KID_B_AYN], kk, d.ayn);
+        stg(bd.f[KID_B_BXN], kk, d.bxn); stg(bd.f[KID_B_BYN], kk, d.byn);
         stg(bd.f[KID_B_XI], kk, d.xi); stg(bd.f[KID_B_YJ], kk, d.yj);
+        // (a berg of the hot build never changes its cell, yet it stores it: leaving the two stores to the re-binning instance
+        // measured 2.5 us per step, inside the run-to-run spread -- DESIGN section 4, round 7)
         stg(bd.i[KID_BI_INE], kk, d.ine); stg(bd.i[KID_BI_JNE], kk, d.jne);
         if (!RK) { stg(bd.f[KID_B_UVEL_PREV], kk, d.uvel_prev); stg(bd.f[KID_B_VVEL_PREV], kk, d.vvel_prev); }
       }
@@ -506,7 +528,8 @@ __global__ void KID_NUM_VGPR_ATTR __launch_bounds__(FAST ? KID_HOT_WG : 256, (Ho
       } else thermodynamics<false, K>(g, p, cellv, t, e, d.uvel, d.vvel, d.lat, d.ine, d.jne, active, acc, ncell, sg, scal);
       if (active) {
         stg(bd.f[KID_B_MASS], kk, t.M); stg(bd.f[KID_B_THICKNESS], kk, t.T); stg(bd.f[KID_B_WIDTH], kk, t.W); stg(bd.f[KID_B_LENGTH], kk, t.L);
-        if (REBIN || t.mass_of_bits != before.mass_of_bits) stg(bd.f[KID_B_MASS_OF_BITS], kk, t.mass_of_bits);
+        // (REBIN: a field the permutation leaves in place -- known as zeros when it was planned -- is not among the new arrays)
+        if ((REBIN && (rb_moved & rb_bit(KID_B_MASS_OF_BITS)) != 0ull) || t.mass_of_bits != before.mass_of_bits) stg(bd.f[KID_B_MASS_OF_BITS], kk, t.mass_of_bits);
         if (Fl<K>::has_fl(fl)) {
           stg(bd.f[KID_B_MASS_OF_FL_BITS], kk, t.mass_of_fl_bits); stg(bd.f[KID_B_MASS_OF_FL_BERGY_BITS], kk, t.mass_of_fl_bergy_bits);
           stg(bd.f[KID_B_FL_K], kk, t.fl_k);

@@ -1107,6 +1107,11 @@ __device__ __forceinline__ void rk4_step(const DevGrid &g, const kid_params &p, 
     rotpos_from_tang(p, xn, yn, lonn, latn);
     rotvec_from_tang(p, lonn, xdotn, ydotn, uveln, vveln);
     rotvec_from_tang(p, lonn, xddotn, yddotn, axn, ayn);  // bxn,byn stay as the 4th accel left them
+    // Every stage's axn, ayn is 0 (accel<RK>), so the rotation is one of zeros: a zero whose sign depends on the longitude.  A plain
+    // hot build that knows the field as zeros puts +0. in its place without looking (Redo::zero), so +0. is what is stored here
+    // (the only reader of the sign is u_star = axn dt/2 + uvel0 of the next step's accel, and only for uvel0 = -0.; a NaN
+    // longitude, whose rotation of zeros would be NaN, leaves 0. here too: lon, lat and the velocities still carry the NaN)
+    axn = 0.; ayn = 0.;
   } else {
     lonn = kid_fma(dt_6, rk_sum(Au, Bu), lon1);
     latn = kid_fma(dt_6, rk_sum(Av, Bv), lat1);

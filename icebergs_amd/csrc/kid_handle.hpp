@@ -83,7 +83,8 @@ struct kid_handle {
   int *d_redo_list2 = nullptr, *d_redo_count2 = nullptr;
   int *d_redo_cnt[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // [part][parity]: a step's counters are zeroed by its prepass
   int redo_parity = 0; bool redo_prezeroed = false, acc_prezeroed = false;
-  bool uploaded_nonzero[KID_NB_F64] = {};  // fields that held anything but zeros at the last upload
+  kid::ZeroState zs;                       // per field: held anything but zeros at the last upload; a launch since may have written it non-zero (kid_rows_plan.hpp)
+  unsigned long long hot_zero_mask = 0ull; // fields the last hot-build launch treated as zeros, one bit per KID_B_* (kid_hot_zero_mask: tests, A/B runs)
   bool tail_valid = false;                 // the dead rows are exactly the tail (true between a re-binning and the next launch)
   bool mig_mode = false;                   // the host exchanges bergs with other handles (kid_migrate.inc): dead rows waiting to be packed are kept
   int32_t *d_keep = nullptr;               // layout flags of such a run (keep_flags_kernel)
@@ -102,9 +103,9 @@ struct kid_handle {
   ForcingSet fset[2]; int forc_parity = 0;
   // A/B switches for measurements and tests, read from the environment ONCE, when the handle is created (nothing on the
   // stepping path calls getenv): KID_MTS_NO_GRAPH, KID_STABLE_RESORT, KID_NO_PLAIN_BUILD, KID_FL_UNFUSED, KID_NEW_ORDER_UNFUSED,
-  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_CHKSUM_TIMING (kid_bergs_chksum_device prints the times of its parts), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
+  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_NO_ZERO_SKIP (the plain hot builds load and store every field, the row permutation moves the fields known to be zero), KID_CHKSUM_TIMING (kid_bergs_chksum_device prints the times of its parts), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
   // fall-back), KID_MTS_POLL_LIMIT (spins before a lane of that kernel gives up: tests of the time-out)
-  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false, rebin_eager = false, chksum_timing = false;
+  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false, rebin_eager = false, chksum_timing = false, no_zero_skip = false;
                      int mts_fused_blocks_cap = 0, mts_poll_limit = 0; } dbg;
   int32_t *d_iceberg_counter = nullptr;  // grd%iceberg_counter_grd (FW:1017)
   bool fl_place_warm = false;
@@ -120,7 +121,7 @@ struct kid_handle {
   // numbers or the pointer tables runs the copy first (rebin_flush).  Nothing of this state is visible from outside.
   bool rebin_pending = false;
   int64_t rebin_fused_count = 0;   // re-binnings taken by that launch so far (kid_rebin_fused_count: tests, A/B runs)
-  struct RebinPlan { PermTable t{}; int moved_f[KID_NB_F64] = {}; int nmf = 0; unsigned long long moved = 0ull; const unsigned *perm = nullptr; long long n = 0; } rplan;
+  struct RebinPlan { PermTable t{}; int moved_f[KID_NB_F64] = {}; int nmf = 0; unsigned long long moved = 0ull, zero_skipped = 0ull; const unsigned *perm = nullptr; long long n = 0; } rplan;
   RebinTab *d_rb = nullptr;     // device table of the re-binning instance of the plain hot builds
   unsigned *d_cell_hist = nullptr; Scratch cscan_tmp; bool stable_resort = false;
   int resort_interval = 16, steps_since_sort = 0;

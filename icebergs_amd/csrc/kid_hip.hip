@@ -185,6 +185,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   h->dbg.stable_resort = getenv("KID_STABLE_RESORT") != nullptr; h->dbg.no_plain_build = getenv("KID_NO_PLAIN_BUILD") != nullptr;
   h->dbg.fl_unfused = getenv("KID_FL_UNFUSED") != nullptr; h->dbg.new_order_unfused = getenv("KID_NEW_ORDER_UNFUSED") != nullptr;
   h->dbg.rebin_eager = getenv("KID_REBIN_EAGER") != nullptr; h->dbg.chksum_timing = getenv("KID_CHKSUM_TIMING") != nullptr;
+  h->dbg.no_zero_skip = getenv("KID_NO_ZERO_SKIP") != nullptr;
   h->dbg.mts_always_label = getenv("KID_MTS_ALWAYS_LABEL") != nullptr; h->dbg.mts_no_fused = getenv("KID_MTS_NO_FUSED") != nullptr;
   if (const char *e = getenv("KID_MTS_FUSED_BLOCKS_CAP")) h->dbg.mts_fused_blocks_cap = atoi(e);
   if (const char *e = getenv("KID_MTS_POLL_LIMIT")) h->dbg.mts_poll_limit = atoi(e);
@@ -451,6 +452,7 @@ int kid_footloose_calving(kid_handle *h) {
   rc = refresh_tables(h);
   if (rc) return rc;
   h->flags.has_fl = 1;
+  h->zs.launched_other();   // (parents lose their bits, children copy what their parents hold)
   // auto-reserve: min_free rows behind the parents before the launch (no retry afterwards: the parents' bits are spent by then)
   rc = auto_reserve(h, h->n + h->auto_min_free, "kid_footloose_calving");
   if (rc) return rc;
@@ -521,6 +523,11 @@ int kid_last_redo_count(kid_handle *h, int64_t *count) {
 int kid_rebin_fused_count(kid_handle *h, int64_t *count) {
   if (!h || !count) return KID_EINVAL;
   *count = h->rebin_fused_count;
+  return KID_OK;
+}
+int kid_hot_zero_mask(kid_handle *h, uint64_t *mask) {
+  if (!h || !mask) return KID_EINVAL;
+  *mask = (uint64_t)h->hot_zero_mask;
   return KID_OK;
 }
 int kid_profile_enable(kid_handle *h, int on) {

@@ -50,9 +50,13 @@ template <bool RK, bool OLD, unsigned PH, bool STAGE>
 static int launch_hot(kid_handle *h, const BergLaunch &c, hipStream_t s, const Redo &redo, bool rebin = false) {
   const unsigned nbp = (unsigned)((redo.klen + KID_HOT_WG - 1) / KID_HOT_WG);
   const int k = hot_build_k(RK, OLD, PH, c.plain, c.flprof, h->flags.store_env != 0, STAGE);
+  h->hot_zero_mask = 0ull;   // (every build but the plain ones loads and stores every field)
   if constexpr (hot_build_k(RK, OLD, PH, true, false, false, STAGE) == 1) {   // (RK, OLD, PH) has plain builds
     if (k == 1 || k == 3) {
-      kid::launch_hot_plain(k == 3, rebin, nbp, (void *)s, c.gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &redo);
+      // the fields this launch need not load or store: zeros in every row (known_zero_mask; the launch's own marks are set by now)
+      Redo plain = redo;
+      plain.zero = h->hot_zero_mask = known_zero_mask(h);
+      kid::launch_hot_plain(k == 3, rebin, nbp, (void *)s, c.gtab, h->d_params, h->d_bp, (long long)h->n, h->d_acc, h->ncell, &h->flags, &plain);
       KID_HIP(h, hipGetLastError());
       return KID_OK;
     }
@@ -119,7 +123,11 @@ template <unsigned PH>
 static int rebin_take_or_flush(kid_handle *h, bool whole, RebinTab &rtab, bool &fused) {
   fused = false;
   if (!h->rebin_pending) return KID_OK;
-  fused = PH == PH_STEP && rebin_fusable(h) && whole && h->rplan.n == h->n && rebin_table(h, h->flags.store_env ? 3 : 1, rtab);
+  // (Purely defensive: a field the plan left in place as zeros that this launch may write would have the launch store rows into
+  // the array other lanes still read theirs from.  No sequence reaches it today -- whatever sets a mark flushes the pending
+  // re-binning first or makes the step non-fusable -- the condition keeps that from depending on call sites elsewhere.)
+  fused = PH == PH_STEP && rebin_fusable(h) && whole && h->rplan.n == h->n && (h->rplan.zero_skipped & ~known_zero_mask(h)) == 0ull &&
+          rebin_table(h, h->flags.store_env ? 3 : 1, rtab);
   return fused ? KID_OK : rebin_flush(h);
 }
 static int rebin_bind(kid_handle *h, const RebinTab &rtab, Redo &redo) {
@@ -179,6 +187,8 @@ static int launch_phase(kid_handle *h, long long range_k0 = 0, long long range_l
     h->err = "this entry point reads the bergs' stored environment, which kid_set_store_environment has switched off (use kid_run_step, or switch it on)";
     return KID_EINVAL;
   }
+  h->zs.launched_berg((PH & PH_EVOLVE) != 0, (PH & PH_THERMO) != 0, h->params.Runge_not_Verlet != 0, h->params.bergy_bit_erosion_fraction == 0.,
+                      h->flags.has_fl != 0, (PH & PH_FL) != 0);
   int rc = repro_refuse(h);
   if (!rc) rc = lanes_drain(h);
   RebinTab rtab;
@@ -236,6 +246,7 @@ static int launch_berg_lanes(kid_handle *h) {
   { const int rc_f = rebin_flush(h); if (rc_f) return rc_f; }   // (this schedule re-bins inside the step, with the copy)
   { int rc_t = refresh_tables(h); if (rc_t) return rc_t; }
   const BergLaunch c = berg_launch(h);
+  h->zs.launched_berg(true, true, h->params.Runge_not_Verlet != 0, h->params.bergy_bit_erosion_fraction == 0., h->flags.has_fl != 0, false);
   hipStream_t M = h->stream, S = h->side_stream;
   const int s = h->lane_step, par = s & 1;
   rows_killed(h);

@@ -374,6 +374,7 @@ int kid_evolve_icebergs_mts(kid_handle *h) {
   if (!h->params.mts) { h->err = "kid_evolve_icebergs_mts needs mts=T"; return KID_EINVAL; }
   int rc = mts_prologue(h);
   if (rc || h->n == 0) return rc;
+  h->zs.launched_other();   // (writes axn, ayn of any row)
   const kid_params &p = h->params;
   const long long n = h->n;
   const DevGrid g = dev_grid(h);
@@ -491,6 +492,7 @@ int kid_evolve_icebergs_interactive(kid_handle *h) {
   if (p.mts || !p.interactive_icebergs_on) { h->err = "kid_evolve_icebergs_interactive: needs interactive_icebergs_on and mts=F"; return KID_EINVAL; }
   int rc = mts_prologue(h);
   if (rc || h->n == 0) return rc;
+  h->zs.launched_other();   // (writes axn, ayn of any row)
   const long long n = h->n;
   const DevGrid g = dev_grid(h);
   hipLaunchKernelGGL(sts_ia_velocity_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);

@@ -138,8 +138,9 @@ static void rows_replaced(kid_handle *h, const kid_berg_soa *host) {
   bool any_static = false, any_fl = false;
   for (int f = 0; f < KID_NB_F64; ++f) {
     bool nz = false;
-    if (host->f64[f]) for (size_t k = 0; k < n && !nz; ++k) nz = host->f64[f][k] != 0.;
-    h->uploaded_nonzero[f] = nz;
+    // (-0. counts as something else than zeros: a build that skips the field would leave it where another stores +0.)
+    if (host->f64[f]) for (size_t k = 0; k < n && !nz; ++k) nz = host->f64[f][k] != 0. || std::signbit(host->f64[f][k]);
+    h->zs.uploaded(f, nz);
     any_static = any_static || (nz && marks_has_static(f)); any_fl = any_fl || (nz && marks_has_fl(f));
   }
   h->flags.has_static = any_static ? 1 : 0;
@@ -159,7 +160,7 @@ static void rows_killed(kid_handle *h) { h->tail_valid = false; }
 static void rows_located(kid_handle *h) {
   rows_orders_stale(h);
   rows_killed(h);
-  h->uploaded_nonzero[KID_B_XI] = true; h->uploaded_nonzero[KID_B_YJ] = true;
+  h->zs.uploaded_nonzero[KID_B_XI] = true; h->zs.uploaded_nonzero[KID_B_YJ] = true;
 }
 // calving, footloose calving, immigrants: rows [n, n + m) were written.  records: the m wire records they were decoded from
 // (kid_rows_plan.hpp), or NULL for rows a kernel wrote -- those may hold anything in any field.  The kernels bound their own
@@ -169,19 +170,20 @@ static int rows_appended(kid_handle *h, int64_t m, const double *records, const 
   rows_orders_stale(h);
   h->tail_valid = false;   // live rows now stand behind whatever dead tail a re-binning left
   if (!h->params.old_interp_flds_order) h->env_ever_stored = true;   // new rows carry an interpolated environment
-  if (!records) for (bool &nz : h->uploaded_nonzero) nz = true;
+  if (!records) h->zs.appended_by_kernel();
   else {
     for (int64_t q = 0; q < m; ++q)
       for (int w = 0; w < MIG_WIDTH; ++w) {
-        if (WIRE_RECORD[w].kind != WIRE_F64 || records[(size_t)q * MIG_WIDTH + w] == 0.) continue;
+        const double word = records[(size_t)q * MIG_WIDTH + w];
+        if (WIRE_RECORD[w].kind != WIRE_F64 || (word == 0. && !std::signbit(word))) continue;
         const int f = WIRE_RECORD[w].field;
-        h->uploaded_nonzero[f] = true;
+        h->zs.appended_word(f);
         if (marks_has_static(f)) h->flags.has_static = 1;
         if (marks_has_fl(f)) h->flags.has_fl = 1;
       }
     // the decode resets the *_old members to the current ones (FW:3573-3577)
-    h->uploaded_nonzero[KID_B_UVEL_OLD] |= h->uploaded_nonzero[KID_B_UVEL]; h->uploaded_nonzero[KID_B_VVEL_OLD] |= h->uploaded_nonzero[KID_B_VVEL];
-    h->uploaded_nonzero[KID_B_LON_OLD] |= h->uploaded_nonzero[KID_B_LON]; h->uploaded_nonzero[KID_B_LAT_OLD] |= h->uploaded_nonzero[KID_B_LAT];
+    h->zs.uploaded_nonzero[KID_B_UVEL_OLD] |= h->zs.uploaded_nonzero[KID_B_UVEL]; h->zs.uploaded_nonzero[KID_B_VVEL_OLD] |= h->zs.uploaded_nonzero[KID_B_VVEL];
+    h->zs.uploaded_nonzero[KID_B_LON_OLD] |= h->zs.uploaded_nonzero[KID_B_LON]; h->zs.uploaded_nonzero[KID_B_LAT_OLD] |= h->zs.uploaded_nonzero[KID_B_LAT];
   }
   if (m > h->capacity - h->n) {
     h->err = full;
@@ -258,6 +260,12 @@ static bool field_never_written(const kid_handle *h, int f) {
   return kid::field_never_written(NeverWrittenIn{p.footloose != 0, p.mts != 0, h->calving_on, p.periodic_reentry != 0, p.Runge_not_Verlet != 0,
                                                  h->flags.has_fl != 0, h->env_ever_stored}, f);
 }
+// The fp64 fields a launch enqueued now -- or a row permutation planned now -- may treat as zeros in every row, a bit per field
+// (kid_rows_plan.hpp).  KID_NO_ZERO_SKIP: none
+static unsigned long long known_zero_mask(const kid_handle *h) {
+  if (h->dbg.no_zero_skip) return 0ull;
+  return kid::known_zero_mask(h->zs, field_never_written(h, KID_B_HEAT_DENSITY), h->params.Runge_not_Verlet != 0, h->params.bergy_bit_erosion_fraction == 0.);
+}
 // The second set of field arrays and the sort / scan storage of a row permutation, at the first compaction or re-binning
 static int perm_storage(kid_handle *h) {
   if (h->d_key[0]) return KID_OK;
@@ -284,8 +292,12 @@ static void perm_fields(kid_handle *h, const unsigned *perm, long long n) {
   kid_handle::RebinPlan &pl = h->rplan;
   pl = kid_handle::RebinPlan{};
   PermTable &t = pl.t;
+  const unsigned long long zeros = known_zero_mask(h);
   for (int f = 0; f < KID_NB_F64; ++f) {
-    if (!h->uploaded_nonzero[f] && field_never_written(h, f)) continue;  // all zeros, before and after
+    if (!h->zs.uploaded_nonzero[f] && field_never_written(h, f)) continue;  // all zeros, before and after
+    // zeros now, though a later launch may write it (axn, ayn, mass_of_bits): it stays in the array it is in, which is the one
+    // every later launch and copy uses.  A fused re-binning launch that no longer knows it as zeros copies first (rebin_take_or_flush)
+    if ((zeros >> f) & 1ull) { pl.zero_skipped |= 1ull << f; continue; }
     t.src[t.n8] = h->bp.f[f]; t.dst[t.n8] = h->bp_alt.f[f]; ++t.n8; pl.moved_f[pl.nmf++] = f; pl.moved |= 1ull << f;
   }
   t.src[t.n8] = h->bp.id; t.dst[t.n8] = h->bp_alt.id; ++t.n8;

@@ -67,4 +67,55 @@ constexpr bool field_never_written(const NeverWrittenIn &s, int f) {
   }
 }
 
+// Fields that hold only zeros (== 0.) in every row of [0, n): a plain hot build neither loads nor stores them, a row
+// permutation does not move them.  Two sticky words per field, cleared only by an upload that proves zeros:
+//   uploaded_nonzero: the field held something else at the last upload, or in a row appended since (a record that carries it,
+//                     or rows a kernel wrote: those may hold anything)
+//   launched_nonzero: a launch that can write it non-zero has been enqueued since the last upload
+// kid_rows.inc calls the row events, kid_launch.inc (and the MTS / interactive / footloose entry points) the launch events;
+// tests/zero_fields_host.cpp enumerates the rule and runs scripted sequences of the events.
+struct ZeroState {
+  bool uploaded_nonzero[KID_NB_F64] = {};
+  bool launched_nonzero[KID_NB_F64] = {};
+  constexpr void uploaded(int f, bool nonzero) { uploaded_nonzero[f] = nonzero; launched_nonzero[f] = false; }
+  constexpr void appended_by_kernel() { for (bool &nz : uploaded_nonzero) nz = true; }
+  constexpr void appended_word(int f) { uploaded_nonzero[f] = true; }   // a non-zero word of an immigrant's record
+  constexpr void launched_accel() { launched_nonzero[KID_B_AXN] = true; launched_nonzero[KID_B_AYN] = true; }
+  // one launch of the per-berg kernel.  Under RK accel ends with axn = ayn = 0 (IB:2286) and the sums of the four stages stay
+  // +0; Verlet stores the explicit part there.  The thermodynamics changes mass_of_bits only with bergy_bit_erosion_fraction > 0
+  // or when footloose bits take the place of a parent that melted (IB:3289)
+  constexpr void launched_berg(bool evolve, bool thermo, bool rk, bool erosion_zero, bool has_fl, bool footloose) {
+    if ((evolve && !rk) || footloose) launched_accel();
+    if ((thermo && (!erosion_zero || has_fl)) || footloose) launched_nonzero[KID_B_MASS_OF_BITS] = true;
+  }
+  // the MTS and the interacting evolve and the footloose calving pass: they write any of the three
+  constexpr void launched_other() { launched_accel(); launched_nonzero[KID_B_MASS_OF_BITS] = true; }
+};
+// what a launch (or the plan of a row permutation) knows about field f now.  never_written: field_never_written above
+struct KnownZeroIn { bool uploaded_nonzero, launched_nonzero, never_written, rk, erosion_zero; };
+constexpr bool field_known_zero(const KnownZeroIn &s, int f) {
+  if (s.uploaded_nonzero) return false;
+  switch (f) {
+    case KID_B_AXN: case KID_B_AYN: return !s.launched_nonzero && s.rk;
+    case KID_B_MASS_OF_BITS: return !s.launched_nonzero && s.erosion_zero;
+    case KID_B_HEAT_DENSITY: return s.never_written;
+    default: return false;
+  }
+}
+// the fields a plain hot build asks about: its mask has one bit per KID_B_* field, and only these are ever set
+constexpr unsigned long long KID_ZERO_FIELDS = (1ull << KID_B_AXN) | (1ull << KID_B_AYN) | (1ull << KID_B_MASS_OF_BITS) | (1ull << KID_B_HEAT_DENSITY);
+static_assert(KID_B_AXN < 64 && KID_B_AYN < 64 && KID_B_MASS_OF_BITS < 64 && KID_B_HEAT_DENSITY < 64, "one bit per fp64 field");
+// the mask of a launch enqueued now.  heat_density_never_written: field_never_written of that field
+constexpr unsigned long long known_zero_mask(const ZeroState &z, bool heat_density_never_written, bool rk, bool erosion_zero) {
+  unsigned long long m = 0ull;
+  for (int f = 0; f < KID_NB_F64; ++f)
+    if (((KID_ZERO_FIELDS >> f) & 1ull) &&
+        field_known_zero(KnownZeroIn{z.uploaded_nonzero[f], z.launched_nonzero[f], f == KID_B_HEAT_DENSITY && heat_density_never_written, rk, erosion_zero}, f))
+      m |= 1ull << f;
+  // the two components of one vector: known together or not at all
+  constexpr unsigned long long accel = (1ull << KID_B_AXN) | (1ull << KID_B_AYN);
+  if ((m & accel) != accel) m &= ~accel;
+  return m;
+}
+
 }  // namespace kid

@@ -37,7 +37,7 @@ module kid_hip_mod
   public :: kid_num_traj_records, kid_profile_enable, kid_profile_get, kid_restart_count_bergs
   public :: kid_restart_read_bergs, kid_restart_read_bonds, kid_restart_write_bergs, kid_restart_write_bonds
   public :: kid_set_conglom_ids, kid_set_forcing_device, kid_set_iceberg_counter, kid_set_resort_interval
-  public :: kid_set_reproducible_sums, kid_rebin_fused_count, kid_memory_in_use
+  public :: kid_set_reproducible_sums, kid_rebin_fused_count, kid_hot_zero_mask, kid_memory_in_use
   public :: kid_set_side_stream, kid_set_store_environment, kid_set_stream, kid_sizeof, kid_step_prepare
   public :: kid_upload_bonds, kid_version
   public :: kid_initialize_bonds, kid_count_bonds
@@ -425,6 +425,11 @@ module kid_hip_mod
       import :: c_int, c_ptr, c_int64_t
       type(c_ptr), value :: h
       integer(c_int64_t), intent(out) :: count
+    end function
+    integer(c_int) function kid_hot_zero_mask(h, mask) bind(C, name='kid_hot_zero_mask')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int64_t), intent(out) :: mask   ! uint64_t: one bit per KID_B_* member
     end function
     integer(c_int) function kid_memory_in_use(device_bytes, pinned_bytes) bind(C, name='kid_memory_in_use')
       import :: c_int, c_int64_t

@@ -717,6 +717,12 @@ class Icebergs:
         self._check(self.lib.kid_rebin_fused_count(self.h, C.byref(c)), "kid_rebin_fused_count")
         return c.value
 
+    def hot_zero_mask(self):
+        """fields the last hot-build launch neither loaded nor stored, as a set of member names (include/kid.h); empty with KID_NO_ZERO_SKIP=1"""
+        m = C.c_uint64()
+        self._check(self.lib.kid_hot_zero_mask(self.h, C.byref(m)), "kid_hot_zero_mask")
+        return {name for f, name in enumerate(T.BERG_F64_NAMES) if (m.value >> f) & 1}
+
     def profile(self, on=True):
         self._check(self.lib.kid_profile_enable(self.h, 1 if on else 0), "kid_profile_enable")
 

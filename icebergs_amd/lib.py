@@ -19,7 +19,7 @@ SYMBOLS = [
     "kid_evolve_icebergs", "kid_footloose_calving", "kid_set_footloose_step", "kid_get_footloose_step", "kid_footloose_uniform", "kid_adjust_fl_berg_interactivity", "kid_thermodynamics", "kid_create_gridded_icebergs_fields",
     "kid_set_store_environment", "kid_set_reproducible_sums", "kid_set_iceberg_counter", "kid_get_iceberg_counter", "kid_step_local", "kid_step_gather", "kid_run_step", "kid_get_accumulators", "kid_accum_device_ptr", "kid_accum_live_count",
     "kid_bind_accum_buffer", "kid_bind_spread_mass_old", "kid_profile_enable", "kid_profile_get",
-    "kid_last_redo_count", "kid_rebin_fused_count", "kid_set_side_stream", "kid_step_prepare", "kid_upload_bonds", "kid_download_bonds", "kid_evolve_icebergs_mts", "kid_set_conglom_ids", "kid_evolve_icebergs_interactive",
+    "kid_last_redo_count", "kid_rebin_fused_count", "kid_hot_zero_mask", "kid_set_side_stream", "kid_step_prepare", "kid_upload_bonds", "kid_download_bonds", "kid_evolve_icebergs_mts", "kid_set_conglom_ids", "kid_evolve_icebergs_interactive",
     "kid_initialize_bonds", "kid_count_bonds",
     "kid_budget", "kid_stock", "kid_incr_mass",
     "kid_ingest_forcing", "kid_get_forcing",
@@ -118,7 +118,7 @@ def load():
     lib.kid_unpack_halo_fold.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.kid_fold_halo_self.argtypes = [H, C.c_int32, C.c_int32]
     lib.kid_read_restart.argtypes = [H, C.c_char_p]
-    older = ("kid_rebin_fused_count", "kid_locate_bergs", "kid_set_restart_locate", "kid_bergs_chksum_device", "kid_checksum_gridded")   # absent from an older build loaded through KID_HIP_SO for an A/B run
+    older = ("kid_rebin_fused_count", "kid_hot_zero_mask", "kid_locate_bergs", "kid_set_restart_locate", "kid_bergs_chksum_device", "kid_checksum_gridded")   # absent from an older build loaded through KID_HIP_SO for an A/B run
     if hasattr(lib, "kid_locate_bergs"):
         lib.kid_locate_bergs.argtypes = [H, C.c_int, C.POINTER(C.c_int64)]
         lib.kid_set_restart_locate.argtypes = [H, C.c_int]
@@ -128,6 +128,8 @@ def load():
     lib.kid_last_redo_count.argtypes = [H, C.POINTER(C.c_int64)]
     if hasattr(lib, "kid_rebin_fused_count"):   # (absent from an older build loaded through KID_HIP_SO for an A/B run)
         lib.kid_rebin_fused_count.argtypes = [H, C.POINTER(C.c_int64)]
+    if hasattr(lib, "kid_hot_zero_mask"):
+        lib.kid_hot_zero_mask.argtypes = [H, C.POINTER(C.c_uint64)]
     lib.kid_upload_bonds.argtypes = [H, C.POINTER(T.BondSoA)]
     lib.kid_download_bonds.argtypes = [H, C.POINTER(T.BondSoA)]
     lib.kid_evolve_icebergs_mts.argtypes = [H]

@@ -513,6 +513,12 @@ int kid_last_redo_count(kid_handle *h, int64_t *count);
  * the step that followed, instead of a launch of its own.  Diagnostic: results never depend on it; KID_REBIN_EAGER=1 in the
  * environment at kid_create keeps it at zero. */
 int kid_rebin_fused_count(kid_handle *h, int64_t *count);
+/* The per-berg fields the most recent hot-build launch treated as zeros -- neither loaded nor stored -- one bit per KID_B_*
+ * member: axn, ayn (an RK run since the upload), mass_of_bits (bergy_bit_erosion_fraction = 0, no footloose), heat_density
+ * (calving off), each only while the upload held zeros there and no launch since could have written anything else.  0 for every
+ * build but the plain hot builds.  Diagnostic: results never depend on it; KID_NO_ZERO_SKIP=1 in the environment at
+ * kid_create keeps it at zero. */
+int kid_hot_zero_mask(kid_handle *h, uint64_t *mask);
 int kid_profile_get(kid_handle *h, double *berg_kernel_ms_total, int64_t *berg_kernel_launches,
                     double *all_ms_total);
 
