@@ -84,6 +84,42 @@ def population(contact):
     return grid(), b
 
 
+# ---- the box on a lat-lon patch: the promotion pass with grid_is_latlon (IB:2816-2822) ----
+LATLON_CENTRE = (300.0, -70.0)
+LATLON_SEED, LATLON_KEEP, LATLON_CHILDREN = 208, 0.5, 0.4
+
+
+def latlon_grid(p):
+    """a single tile of HB's 16 x 12 cells, 5 km tall and 5 km wide at the box's centre"""
+    import latlon_bonded as LB
+    dlat = HB.RES / (p.Rearth * np.pi / 180.0)
+    return LB.latlon_patch(p, LATLON_CENTRE[0], LATLON_CENTRE[1], (0.5 * HB.NI * HB.NTX + 0.5, 0.5 * HB.NJ * HB.NTY + 0.5),
+                           ni=HB.NI * HB.NTX, nj=HB.NJ * HB.NTY, dlat=dlat)
+
+
+def latlon_state(contact):
+    """(grid, params, bergs): the halo-berg box's discs mapped by tests/latlon_bonded.py's map (metres from the box's centre to
+    degrees), thinned to about LATLON_KEEP of them so that some stand alone, LATLON_CHILDREN of the rest waiting at fl_k = -1;
+    rows in reference order.  Chosen with np_adjust alone: both searches promote some and hold some back, and no decision is
+    closer to its threshold than MARGIN (tests/test_fl_interactive_cpu.py)."""
+    import latlon_bonded as LB
+    p = params(contact)
+    g = latlon_grid(p)
+    _, b0 = HB.population(SEED)
+    rng = np.random.default_rng(LATLON_SEED)
+    keep = np.nonzero(rng.random(len(b0["lon"])) < LATLON_KEEP)[0]
+    b = {k: (v[keep].copy() if isinstance(v, np.ndarray) else v) for k, v in b0.items()}
+    x, y = b["lon"] - 0.5 * HB.NI * HB.NTX * HB.RES, b["lat"] - 0.5 * HB.NJ * HB.NTY * HB.RES
+    b["lon"][:], b["lat"][:] = LB.to_degrees(p, LATLON_CENTRE[0], LATLON_CENTRE[1], x, y)
+    for f in ("lon_old", "start_lon"):
+        b[f][:] = b["lon"]
+    for f in ("lat_old", "start_lat"):
+        b[f][:] = b["lat"]
+    LB.locate(g, b)
+    b["fl_k"][:] = np.where(rng.random(len(keep)) < LATLON_CHILDREN, -1.0, rng.uniform(0.0, 6.0e4, len(keep)))
+    return g, p, S.sort_reference_order(b)
+
+
 # ---- adjust_fl_berg_interactivity, IB:2765-2841 ----
 def np_adjust(p, desc, b, n, margins=None):
     """the rows whose fl_k the pass sets to -2, in row order; b["fl_k"] is changed.  The pass writes a berg's own fl_k only and

@@ -103,47 +103,92 @@ def bond_set(bergs, bonds, only_unbroken=False):
     return out
 
 
-def compare_mts(ref, refbd, got, gotbd, label="", tol=1.0e-9, stiff_tol=1.0e-4):
-    """MTS/DEM: rows are stable (no re-binning), so bergs and bonds are compared row by row.  The set of bonds and the
-    set of broken bonds must be identical; states within `tol` (relative to the field max)."""
-    rb, gb = ref[0], got[0]
-    assert np.array_equal(rb["id"], gb["id"]) and np.array_equal(rb["alive"], gb["alive"]), label + ": rows differ"
-    for f in ("ine", "jne", "conglom_id", "n_bonds"):
-        assert np.array_equal(rb[f], gb[f]), "%s: %s differs" % (label, f)
-    rep = {}
-    # The DEM springs are stiff (dem_spring_coef*T ~ 1e9 N/m): a bond force is a difference of positions that agree to
-    # the last bit or two, so forces, stresses and the accelerations built from them carry a relative error of
-    # ~1e-16 * |x| * k / |F| -- they are compared at `stiff_tol`, positions/velocities/rotations at `tol`.
-    stiff = {"axn", "ayn", "bxn", "byn", "axn_fast", "ayn_fast", "bxn_fast", "byn_fast", "ang_accel"}
+STIFF_FIELDS = {"axn", "ayn", "bxn", "byn", "axn_fast", "ayn_fast", "bxn_fast", "byn_fast", "ang_accel"}
+LON_FIELDS = {"lon", "lon_old"}
+MTS_EXACT = ("rows", "ine", "jne", "conglom_id", "n_bonds", "bond_count", "bond_partners", "broken_bonds", "scalars")
+MTS_SCALARS = ("nbergs_melted", "nspeeding_tickets", "nbergs_alive", "error_count", "nbonds_broken")
+
+
+def mts_tolerances(tol=1.0e-9, stiff_tol=1.0e-4):
+    """{key of mts_errors' report: tolerance}, the values compare_mts has always used.
+    The DEM springs are stiff (dem_spring_coef*T ~ 1e9 N/m): a bond force is a difference of positions that agree to
+    the last bit or two, so forces, stresses and the accelerations built from them carry a relative error of
+    ~1e-16 * |x| * k / |F| -- they are compared at `stiff_tol`, positions/velocities/rotations at `tol`."""
+    t = {}
     for f in TRAJ_FIELDS + MTS_FIELDS + SIZE_FIELDS:
-        e = rel_err(gb[f], rb[f])
-        rep[f] = e
-        t = stiff_tol if f in stiff else (1.0e-6 if f in ("ang_vel", "rot") else tol)  # rotation integrates the stiff torques
-        assert e <= t, "%s: %s rel err %.3e > %.1e" % (label, f, e, t)
-    assert np.array_equal(refbd["count"], gotbd["count"]), label + ": bond counts differ"
-    n = len(rb["lon"])
-    live = (np.arange(refbd["max_bonds"])[:, None] < refbd["count"][None, :]).ravel()  # slots past a list's end are stale
-    assert np.array_equal(refbd["other_id"][live], gotbd["other_id"][live]), label + ": bond partners differ"
-    assert np.array_equal(refbd["broken"][live], gotbd["broken"][live]), label + ": set of broken bonds differs"
+        t[f] = stiff_tol if f in STIFF_FIELDS else (1.0e-6 if f in ("ang_vel", "rot") else tol)  # rotation integrates the stiff torques
     for f in BOND_STATE + ["f_x", "f_y", "fd_x", "fd_y", "t", "t_d"]:
-        e = rel_err(gotbd[f][live], refbd[f][live])
-        rep["bond_" + f] = e
-        t = tol if f == "length" else stiff_tol
-        assert e <= t, "%s: bond %s rel err %.3e > %.1e" % (label, f, e, t)
+        t["bond_" + f] = tol if f == "length" else stiff_tol
+    t["acc"] = t["out"] = 10 * TOL_GRID   # velocity-weighted planes carry the DEM velocities
+    return t
+
+
+def wrapped_lon_err(a, b):
+    """rel_err of longitudes after ((a - b + 180) mod 360) - 180: a wrap by 360 is no difference"""
+    scale = np.max(np.abs(b)) if b.size else 0.0
+    d = np.mod(a - b + 180.0, 360.0) - 180.0
+    e = float(np.max(np.abs(d))) if d.size else 0.0
+    return e / scale if scale > 0.0 else e
+
+
+def mts_errors(ref, refbd, got, gotbd, wrap_lon=False):
+    """(report, exact): report = {field: rel err (of the field's max)} with the bond fields as "bond_<name>" and the worst
+    accumulator / output plane as "acc" / "out" (per plane as "acc<k>" / "out<k>"); exact = {name of MTS_EXACT: bool} for what
+    must be identical.  Rows are stable under MTS (no re-binning), so bergs and bonds are compared row by row."""
+    from icebergs_amd import types as T
+    rb, gb = ref[0], got[0]
+    exact = {"rows": bool(np.array_equal(rb["id"], gb["id"]) and np.array_equal(rb["alive"], gb["alive"]))}
+    for f in ("ine", "jne", "conglom_id", "n_bonds"):
+        exact[f] = bool(np.array_equal(rb[f], gb[f]))
+    rep = {}
+    for f in TRAJ_FIELDS + MTS_FIELDS + SIZE_FIELDS:
+        rep[f] = wrapped_lon_err(gb[f], rb[f]) if (wrap_lon and f in LON_FIELDS) else rel_err(gb[f], rb[f])
+    exact["bond_count"] = bool(np.array_equal(refbd["count"], gotbd["count"]))
+    live = (np.arange(refbd["max_bonds"])[:, None] < refbd["count"][None, :]).ravel()  # slots past a list's end are stale
+    exact["bond_partners"] = bool(np.array_equal(refbd["other_id"][live], gotbd["other_id"][live]))
+    exact["broken_bonds"] = bool(np.array_equal(refbd["broken"][live], gotbd["broken"][live]))
+    for f in BOND_STATE + ["f_x", "f_y", "fd_x", "fd_y", "t", "t_d"]:
+        rep["bond_" + f] = rel_err(gotbd[f][live], refbd[f][live])
     sc = acc_scales(ref[1])
     for k in range(ref[1].shape[0]):
-        e = acc_err(got[1], ref[1], k, sc)
-        assert e <= 10 * TOL_GRID, "%s: accumulator plane %d rel err %.3e" % (label, k, e)  # velocity-weighted planes carry the DEM velocities
-    from icebergs_amd import types as T
+        rep["acc%d" % k] = acc_err(got[1], ref[1], k, sc)
     # ustar_iceberg steps from 0 to its value where spread_area becomes non-zero: leave out cells that only hold a
     # rounding-sized sliver of a footprint
     solid = np.abs(ref[2][T.OUT_NAMES["spread_area"]]) > 1.0e-9
     for k in range(ref[2].shape[0]):
         a, b_ = (got[2][k][solid], ref[2][k][solid]) if k == T.OUT_NAMES["ustar_iceberg"] else (got[2][k], ref[2][k])
-        e = rel_err(a, b_)
-        assert e <= 10 * TOL_GRID, "%s: output plane %d rel err %.3e" % (label, k, e)
+        rep["out%d" % k] = rel_err(a, b_)
+    rep["acc"] = max(rep["acc%d" % k] for k in range(ref[1].shape[0]))
+    rep["out"] = max(rep["out%d" % k] for k in range(ref[2].shape[0]))
+    exact["scalars"] = all(ref[3][T.SCALAR_NAMES[name]] == got[3][T.SCALAR_NAMES[name]] for name in MTS_SCALARS)
+    return rep, exact
+
+
+def compare_mts(ref, refbd, got, gotbd, label="", tol=1.0e-9, stiff_tol=1.0e-4, tols=None, wrap_lon=False):
+    """MTS/DEM: the set of bonds and the set of broken bonds must be identical; states within `tol` / `stiff_tol` (relative to
+    the field max, mts_tolerances).  tols: {key: tolerance} that replaces those of the keys it names (a field, "bond_<name>",
+    "acc", "out"); wrap_lon: longitudes are compared modulo 360."""
     from icebergs_amd import types as T
-    for name in ("nbergs_melted", "nspeeding_tickets", "nbergs_alive", "error_count", "nbonds_broken"):
+    t = mts_tolerances(tol, stiff_tol)
+    if tols:
+        t.update(tols)
+    rep, exact = mts_errors(ref, refbd, got, gotbd, wrap_lon)
+    rb = ref[0]
+    assert exact["rows"], label + ": rows differ"
+    for f in ("ine", "jne", "conglom_id", "n_bonds"):
+        assert exact[f], "%s: %s differs" % (label, f)
+    for f in TRAJ_FIELDS + MTS_FIELDS + SIZE_FIELDS:
+        assert rep[f] <= t[f], "%s: %s rel err %.3e > %.1e" % (label, f, rep[f], t[f])
+    assert exact["bond_count"], label + ": bond counts differ"
+    assert exact["bond_partners"], label + ": bond partners differ"
+    assert exact["broken_bonds"], label + ": set of broken bonds differs"
+    for f in BOND_STATE + ["f_x", "f_y", "fd_x", "fd_y", "t", "t_d"]:
+        assert rep["bond_" + f] <= t["bond_" + f], "%s: bond %s rel err %.3e > %.1e" % (label, f, rep["bond_" + f], t["bond_" + f])
+    for k in range(ref[1].shape[0]):
+        assert rep["acc%d" % k] <= t["acc"], "%s: accumulator plane %d rel err %.3e" % (label, k, rep["acc%d" % k])
+    for k in range(ref[2].shape[0]):
+        assert rep["out%d" % k] <= t["out"], "%s: output plane %d rel err %.3e" % (label, k, rep["out%d" % k])
+    for name in MTS_SCALARS:
         k = T.SCALAR_NAMES[name]
         assert ref[3][k] == got[3][k], "%s: scalar %s %r != %r" % (label, name, got[3][k], ref[3][k])
     return rep

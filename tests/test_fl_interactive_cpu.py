@@ -118,6 +118,22 @@ def test_promotion_pass_on_a_hand_made_case():
     assert FI.np_adjust(p, d, b, 5) == []
 
 
+@pytest.mark.parametrize("contact", [False, True])
+def test_latlon_state_takes_the_latlon_branch_with_a_margin(contact):
+    """the box on a lat-lon patch (FI.latlon_state): np_adjust takes its grid_is_latlon branch, promotes some children and holds
+    some back, no decision is closer to its threshold than MARGIN, and the other branch would decide differently"""
+    g, p, b = FI.latlon_state(contact)
+    n = len(b["lon"])
+    assert g["desc"].grid_is_latlon == 1 and p.Rearth == 6.36e6 and np.abs(b["lat"]).min() > 69.0
+    children = int((b["fl_k"] == -1.0).sum())
+    margins, w = [], S.copy_bergs(b)
+    rows = FI.np_adjust(p, g["desc"], w, n, margins)
+    print("lat-lon %s: %d rows, %d children, %d promoted, smallest margin %.1e" % ("contact" if contact else "3x3", n, children, len(rows), min(margins)))
+    assert 3 <= len(rows) <= children - 10 and min(margins) >= FI.MARGIN
+    flat = S.cartesian_grid(HB.NI * HB.NTX, HB.NJ * HB.NTY, HB.RES)["desc"]     # the same cells, grid_is_latlon = 0: degrees taken for metres
+    assert FI.np_adjust(p, flat, S.copy_bergs(b), n) != rows
+
+
 def test_fl_contact_under_sanitizers(tmp_path):
     cxx = None
     for c in (os.environ.get("CXX"), "g++", "clang++", "/opt/rocm/llvm/bin/clang++"):

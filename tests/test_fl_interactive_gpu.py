@@ -201,6 +201,30 @@ def test_the_call_on_its_own(contact):
         ib.close()
 
 
+@pytest.mark.parametrize("contact", SEARCHES)
+def test_the_call_on_a_latlon_grid(contact):
+    """the box's discs on a lat-lon patch at 70 S (FI.latlon_state, single tile): the pass measures pairs in metres with cos of
+    their mean latitude (IB:2816-2822) and promotes exactly the rows np_adjust's grid_is_latlon branch promotes -- no decision of
+    which is closer to its threshold than MARGIN -- and changes nothing else"""
+    grid, p, state = FI.latlon_state(contact)
+    n = len(state["lon"])
+    want, margins = S.copy_bergs(state), []
+    rows = FI.np_adjust(p, grid["desc"], want, n, margins)
+    assert grid["desc"].grid_is_latlon == 1 and min(margins) >= FI.MARGIN
+    assert 3 <= len(rows) < int((state["fl_k"] == -1.0).sum()), "some children are promoted, some keep waiting"
+    ib = _icebergs(grid, p, n)
+    try:
+        ib.upload_bergs(state)
+        assert ib.adjust_fl_berg_interactivity() == len(rows)
+        got = ib.download_bergs()
+        assert np.array_equal(np.nonzero(got["fl_k"] != state["fl_k"])[0], np.array(rows))
+        for f in ALL_FIELDS:
+            assert np.array_equal(got[f], want[f]), f
+        assert ib.adjust_fl_berg_interactivity() == 0
+    finally:
+        ib.close()
+
+
 def test_refused_while_halo_rows_are_resident():
     """tile (0, 0) of the box holds copies of its east neighbour's bergs: KID_EINVAL by name, whatever the namelist says of footloose"""
     whole, b = HB.population()
