@@ -103,9 +103,9 @@ struct kid_handle {
   ForcingSet fset[2]; int forc_parity = 0;
   // A/B switches for measurements and tests, read from the environment ONCE, when the handle is created (nothing on the
   // stepping path calls getenv): KID_MTS_NO_GRAPH, KID_STABLE_RESORT, KID_NO_PLAIN_BUILD, KID_FL_UNFUSED, KID_NEW_ORDER_UNFUSED,
-  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_NO_ZERO_SKIP (the plain hot builds load and store every field, the row permutation moves the fields known to be zero), KID_CHKSUM_TIMING (kid_bergs_chksum_device prints the times of its parts), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
+  // KID_MTS_ALWAYS_LABEL, KID_MTS_NO_FUSED, KID_REBIN_EAGER (every re-binning copies the rows at once), KID_NO_ZERO_SKIP (the plain hot builds load and store every field, the row permutation moves the fields known to be zero), KID_COLD_EAGER (no field is cold: a row permutation moves every member it did before cold fields), KID_CHKSUM_TIMING (kid_bergs_chksum_device prints the times of its parts), KID_MTS_FUSED_BLOCKS_CAP (workgroups the fused sub-step kernel may use: tests of its
   // fall-back), KID_MTS_POLL_LIMIT (spins before a lane of that kernel gives up: tests of the time-out)
-  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false, rebin_eager = false, chksum_timing = false, no_zero_skip = false;
+  struct DebugOpts { bool stable_resort = false, no_plain_build = false, fl_unfused = false, new_order_unfused = false, mts_always_label = false, mts_no_fused = false, rebin_eager = false, chksum_timing = false, no_zero_skip = false, cold_eager = false;
                      int mts_fused_blocks_cap = 0, mts_poll_limit = 0; } dbg;
   int32_t *d_iceberg_counter = nullptr;  // grd%iceberg_counter_grd (FW:1017)
   bool fl_place_warm = false;
@@ -121,7 +121,12 @@ struct kid_handle {
   // numbers or the pointer tables runs the copy first (rebin_flush).  Nothing of this state is visible from outside.
   bool rebin_pending = false;
   int64_t rebin_fused_count = 0;   // re-binnings taken by that launch so far (kid_rebin_fused_count: tests, A/B runs)
-  struct RebinPlan { PermTable t{}; int moved_f[KID_NB_F64] = {}; int nmf = 0; unsigned long long moved = 0ull, zero_skipped = 0ull; const unsigned *perm = nullptr; long long n = 0; } rplan;
+  struct RebinPlan { PermTable t{}; int moved_f[KID_NB_F64] = {}; int nmf = 0; unsigned long long moved = 0ull, zero_skipped = 0ull; const unsigned *perm = nullptr; long long n = 0;
+                     unsigned moved_i32 = 0u; bool moved_id = false, origin_moves = false; } rplan;   // the int32 fields and the id move unless cold; `origin` moves in their place
+  // Cold fields (kid_rows_plan.hpp): while `deferred`, the members of `set` sit where they were when the first permutation left them
+  // out, and field f of row k is bp.f[f][origin[k]].  Everything that reads them by row or changes which rows exist materialises
+  // first (cold_materialise, kid_rows.inc).  materialised: gathers so far
+  struct ColdState { kid::ColdSet set; bool deferred = false; int64_t materialised = 0; int32_t *origin = nullptr, *origin_alt = nullptr; } cold;
   RebinTab *d_rb = nullptr;     // device table of the re-binning instance of the plain hot builds
   unsigned *d_cell_hist = nullptr; Scratch cscan_tmp; bool stable_resort = false;
   int resort_interval = 16, steps_since_sort = 0;
@@ -182,7 +187,9 @@ struct kid_handle {
 // host-side functions used before the file that defines them (the .inc files are included where their kernels belong)
 extern "C" {
 static int refresh_tables(kid_handle *h), join_side(kid_handle *h);
-static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one)
+static int rebin_flush(kid_handle *h);   // run the copy of a pending re-binning (no-op without one) and put the cold fields in row order (cold_materialise)
+static int rebin_flush_rows(kid_handle *h);   // ... the copy alone: for the step and for the callers that never look at a cold field
+static int cold_materialise(kid_handle *h), cold_settle(kid_handle *h);   // kid_rows.inc
 static int rebin_plan(kid_handle *h, bool dead_last);
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count), rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);
 static bool plain_namelist(const kid_handle *h), lanes_eligible(const kid_handle *h);   // kid_launch.inc

@@ -185,7 +185,7 @@ int kid_create(const kid_grid_desc *grid, const kid_params *params, int64_t capa
   h->dbg.stable_resort = getenv("KID_STABLE_RESORT") != nullptr; h->dbg.no_plain_build = getenv("KID_NO_PLAIN_BUILD") != nullptr;
   h->dbg.fl_unfused = getenv("KID_FL_UNFUSED") != nullptr; h->dbg.new_order_unfused = getenv("KID_NEW_ORDER_UNFUSED") != nullptr;
   h->dbg.rebin_eager = getenv("KID_REBIN_EAGER") != nullptr; h->dbg.chksum_timing = getenv("KID_CHKSUM_TIMING") != nullptr;
-  h->dbg.no_zero_skip = getenv("KID_NO_ZERO_SKIP") != nullptr;
+  h->dbg.no_zero_skip = getenv("KID_NO_ZERO_SKIP") != nullptr; h->dbg.cold_eager = getenv("KID_COLD_EAGER") != nullptr;
   h->dbg.mts_always_label = getenv("KID_MTS_ALWAYS_LABEL") != nullptr; h->dbg.mts_no_fused = getenv("KID_MTS_NO_FUSED") != nullptr;
   if (const char *e = getenv("KID_MTS_FUSED_BLOCKS_CAP")) h->dbg.mts_fused_blocks_cap = atoi(e);
   if (const char *e = getenv("KID_MTS_POLL_LIMIT")) h->dbg.mts_poll_limit = atoi(e);
@@ -273,7 +273,7 @@ int kid_set_params(kid_handle *h, const kid_params *params) {
   h->labels_stale = true;   // (the conglomerate labelling reads dem / max_bonds / use_broken_bonds_for_substep_contact)
   h->flags.footprint = footprint_needed(h->params) ? 1 : 0;
   if (!h->params.old_interp_flds_order && !h->env_off_requested) h->flags.store_env = 1;  // the stored environment is an input again
-  return KID_OK;
+  return cold_settle(h);   // the new namelist may read a field that is deferred as cold
 }
 // order the main stream behind general-build launches that are still in flight on the side stream
 static int join_side(kid_handle *h) {
@@ -390,7 +390,7 @@ int kid_set_store_environment(kid_handle *h, int on) {
   if (!h) return KID_EINVAL;
   h->flags.store_env = on ? 1 : 0;
   h->env_off_requested = !on;
-  return KID_OK;
+  return cold_settle(h);
 }
 
 static int refresh_tables(kid_handle *h) {

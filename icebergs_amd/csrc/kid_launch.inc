@@ -126,9 +126,17 @@ static int rebin_take_or_flush(kid_handle *h, bool whole, RebinTab &rtab, bool &
   // (Purely defensive: a field the plan left in place as zeros that this launch may write would have the launch store rows into
   // the array other lanes still read theirs from.  No sequence reaches it today -- whatever sets a mark flushes the pending
   // re-binning first or makes the step non-fusable -- the condition keeps that from depending on call sites elsewhere.)
-  fused = PH == PH_STEP && rebin_fusable(h) && whole && h->rplan.n == h->n && (h->rplan.zero_skipped & ~known_zero_mask(h)) == 0ull &&
+  // (The same for a field the plan left in place as cold that a step of the handle now touches: cold_holds.)
+  fused = PH == PH_STEP && rebin_fusable(h) && whole && h->rplan.n == h->n && (h->rplan.zero_skipped & ~known_zero_mask(h)) == 0ull && cold_holds(h) &&
           rebin_table(h, h->flags.store_env ? 3 : 1, rtab);
-  return fused ? KID_OK : rebin_flush(h);
+  return fused ? KID_OK : rebin_flush_rows(h);
+}
+// Cold fields stay deferred through the plain fused step alone -- the launch their rule was read from (kid_rows_plan.hpp); every
+// other launch of the per-berg kernel finds every field in row order
+template <unsigned PH>
+static int cold_for_launch(kid_handle *h) {
+  if (!h->cold.deferred || (PH == PH_STEP && rebin_fusable(h) && cold_holds(h))) return KID_OK;
+  return cold_materialise(h);
 }
 static int rebin_bind(kid_handle *h, const RebinTab &rtab, Redo &redo) {
   hipLaunchKernelGGL(set_rebin_table_kernel, dim3(1), dim3(64), 0, h->stream, rtab, h->d_rb);
@@ -194,6 +202,7 @@ static int launch_phase(kid_handle *h, long long range_k0 = 0, long long range_l
   RebinTab rtab;
   bool rebin_fused = false;
   if (!rc) rc = rebin_take_or_flush<PH>(h, whole, rtab, rebin_fused);
+  if (!rc) rc = cold_for_launch<PH>(h);
   if (!rc) rc = refresh_tables(h);
   if (rc) return rc;
   const BergLaunch c = berg_launch(h);
@@ -450,6 +459,7 @@ int kid_step_local(kid_handle *h) {   // IB:5409-5512
   if (!rc) rc = repro_refuse(h);
   // a pending re-binning waits for the one launch that can take it (the plain fused step); every other kind of step copies first
   if (!rc && h->rebin_pending && !rebin_fusable(h)) rc = rebin_flush(h);
+  if (!rc && !rebin_fusable(h)) rc = cold_materialise(h);   // (the other families launch kernels that read any field by row)
   if (rc) return rc;
   const kid_params &p = h->params;
   if (p.mts) return step_mts(h);

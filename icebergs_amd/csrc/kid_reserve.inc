@@ -109,6 +109,7 @@ static int reserve_list(kid_handle *h, int64_t new_cap, ReserveList &L) {
   for (auto &field : h->bp_alt.f) L.add(field, RESERVE_LAZY);
   for (auto &field : h->bp_alt.i) L.add(field, RESERVE_LAZY);
   L.add(h->bp_alt.id, RESERVE_LAZY);
+  for (int32_t **q : {&h->cold.origin, &h->cold.origin_alt}) L.add(*q, RESERVE_LAZY);   // (the caller has materialised the cold fields: rows_enter)
   for (unsigned **q : {&h->d_key[0], &h->d_key[1], &h->d_idx[0], &h->d_idx[1], &h->d_cell_hist}) L.add(*q, RESERVE_LAZY);
   for (Scratch *t : {&h->sort_tmp, &h->scan_tmp, &h->cscan_tmp}) L.add(*t, RESERVE_LAZY);
   L.add(h->d_lane_alt, RESERVE_LAZY);

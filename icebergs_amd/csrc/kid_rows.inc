@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) cell_key_kernel(const int32_t *ine, const
   }
 }
 // Counting sort by cell for kid_move_berg_between_cells: (1) key + rank of every berg within its cell (one atomic per
-// berg on the cell's counter), (2) exclusive scan of the counters, (3) destination row = cell start + rank.  Three small
+// distinct cell of a wave on the cell's counter), (2) exclusive scan of the counters, (3) destination row = cell start + rank.  Three small
 // launches instead of the ~20 of a comparison sort of 1e6 pairs; the order of the bergs inside a cell is the order the
 // atomics arrive in (results never depend on the row order, see kid.h).
 __global__ void __launch_bounds__(256) cell_rank_kernel(const int32_t *ine, const int32_t *jne, const int32_t *alive, int isd, int jsd, int ni,
@@ -69,20 +69,33 @@ __global__ void __launch_bounds__(256) cell_rank_kernel(const int32_t *ine, cons
   const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
   const bool in = k < n;
   const unsigned c = in ? (alive[k] ? (unsigned)((ine[k] - isd) + (jne[k] - jsd) * ni) : dead_key) : 0xffffffffu;
-  // the SoA is almost sorted: the lanes of a wave form a few runs of equal cell.  One atomic per run (its head lane
-  // adds the run length), not one per berg: ~14 lanes would otherwise queue on the same address.
+  // the SoA is almost sorted: the lanes of a wave hold a few distinct cells.  One atomic per distinct cell (its first lane adds
+  // the number of lanes that share it), not one per berg -- ~14 lanes would otherwise queue on the same address -- and not one
+  // per run of adjacent lanes either: as the order decays between two re-binnings an out-of-place berg is a run of its own and
+  // splits the run it sits in (7.9 runs against 2.6 cells fifteen steps after a re-binning).  The walk of the hot build
+  // (kid_berg_kernel.hpp): first lane not yet served, its cell by v_readlane, a ballot of the lanes that share it.  The atomics
+  // are issued after the walk, all at once: one round trip per wave, not one per cell.
   const int lane = (int)__lane_id();
-  const unsigned prev = __shfl_up(c, 1);
-  const bool head = (lane == 0) || (prev != c);
-  const unsigned long long heads = __ballot(head);
-  const unsigned long long below = heads & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull));   // heads at or below this lane
-  const int head_lane = 63 - __clzll(below);
-  const unsigned long long above = (lane == 63) ? 0ull : (heads >> (lane + 1));                  // heads after this lane
-  const int next_head = above ? lane + 1 + (__ffsll((long long)above) - 1) : 64;
+  unsigned long long rem = __ballot(in);
+  int leader = lane;
+  unsigned cnt = 0u, place = 0u;
+  while (rem != 0ull) {  // wave-uniform: one turn per distinct cell
+    const int u = (int)__ffsll((long long)rem) - 1;
+    const unsigned cu = (unsigned)__builtin_amdgcn_readlane((int)c, u);
+    const bool mine = in && c == cu;
+    const unsigned long long bm = __ballot(mine);
+    if (mine) { leader = u; cnt = (unsigned)__popcll(bm); place = __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u)); }
+    rem &= ~bm;
+  }
   unsigned base = 0u;
-  if (head && in) base = atomicAdd(hist + c, (unsigned)(next_head - lane));
-  base = __shfl(base, head_lane);
-  if (in) { key[k] = c; rank[k] = base + (unsigned)(lane - head_lane); }
+  if (in && lane == leader) base = atomicAdd(hist + c, cnt);
+  base = __shfl(base, leader);
+  if (in) { key[k] = c; rank[k] = base + place; }
+}
+// the identity of `origin` (cold fields, kid_rows_plan.hpp)
+__global__ void __launch_bounds__(256) iota_i32_kernel(int32_t *p, long long n) {
+  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
+  if (k < n) p[k] = (int32_t)k;
 }
 __global__ void __launch_bounds__(256) cell_place_kernel(const unsigned *key, const unsigned *rank, const unsigned *start, unsigned *perm, unsigned *inv, long long n) {
   const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
@@ -198,11 +211,15 @@ static int rows_appended(kid_handle *h, int64_t m, const double *records, const 
 
 // The prologue of an entry point that looks at rows: on the handle's device, behind whatever the side stream still runs, with
 // no re-binning pending.  ROWS_CHANGE also leaves the slow-lane schedule (its lists hold row numbers; new rows start in the hot lane).
+// Cold fields (kid_rows_plan.hpp) are put in row order too, unless the caller says it touches none of them and keeps the rows
+// that exist (COLD_LEAVE: kid_move_berg_between_cells, kid_num_bergs -- which materialises itself before it drops a tail).
 enum RowsMode { ROWS_READ, ROWS_CHANGE };
-static int rows_enter(kid_handle *h, RowsMode mode) {
+enum RowsCold { COLD_READ, COLD_LEAVE };
+static int rows_enter(kid_handle *h, RowsMode mode, RowsCold cold = COLD_READ) {
   KID_HIP(h, hipSetDevice(h->device));
   const int rc = mode == ROWS_CHANGE ? lanes_drain(h) : join_side(h);
-  return rc ? rc : rebin_flush(h);
+  if (rc) return rc;
+  return cold == COLD_LEAVE ? rebin_flush_rows(h) : rebin_flush(h);
 }
 // rows k < h->n with flags[k] != 0 -- and, with `halo`, halo[k] >= 0.5 too: one launch, one host read
 static int count_rows(kid_handle *h, const int32_t *flags, const double *halo, int64_t *count) {
@@ -235,7 +252,7 @@ static int layout_flags(kid_handle *h, const int32_t **flags) {
 
 int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive) {
   if (!h) return KID_EINVAL;
-  { const int rc = rows_enter(h, ROWS_READ); if (rc) return rc; }
+  { const int rc = rows_enter(h, ROWS_READ, COLD_LEAVE); if (rc) return rc; }   // (counting looks at `alive` only)
   if (n_slots) *n_slots = h->n;
   if (n_alive) {
     int64_t cnt = 0;
@@ -247,6 +264,7 @@ int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive) {
       { const int rc = count_rows(h, flags, nullptr, &cnt); if (rc) return rc; }
     }
     if (h->tail_valid && cnt < h->n) {  // a re-binning left the dead at the tail: drop them now that the count is known
+      { const int rc = cold_materialise(h); if (rc) return rc; }   // the rows that exist change
       rows_truncated(h, cnt);
       if (n_slots) *n_slots = h->n;
     }
@@ -266,6 +284,49 @@ static unsigned long long known_zero_mask(const kid_handle *h) {
   if (h->dbg.no_zero_skip) return 0ull;
   return kid::known_zero_mask(h->zs, field_never_written(h, KID_B_HEAT_DENSITY), h->params.Runge_not_Verlet != 0, h->params.bergy_bit_erosion_fraction == 0.);
 }
+// The cold set of this handle now (kid_rows_plan.hpp).  KID_COLD_EAGER: empty
+static bool rebin_fusable(const kid_handle *h);
+static kid::ColdSet cold_set(const kid_handle *h) {
+  const kid_params &p = h->params;
+  if (h->dbg.cold_eager) return kid::ColdSet{};
+  return kid::cold_set(kid::ColdIn{rebin_fusable(h), p.Runge_not_Verlet != 0, p.periodic_reentry != 0, h->flags.has_static != 0, h->flags.has_fl != 0,
+                                   p.iceberg_bonds_on != 0, (p.diag_mask & KID_DIAG_MELT_BY_CLASS) != 0});
+}
+// only the field pointers changed: one table, not four (a launch on the side stream may still be reading it)
+static int berg_table_follows(kid_handle *h) {
+  if (h->tables_dirty) return refresh_tables(h);
+  { const int rc = join_side(h); if (rc) return rc; }
+  hipLaunchKernelGGL(set_berg_table_kernel, dim3(1), dim3(64), 0, h->stream, h->bp, h->d_bp);
+  KID_HIP(h, hipGetLastError());
+  return KID_OK;
+}
+// Put the deferred cold fields in row order: ONE launch gathers them through `origin` into the second set of arrays, which
+// become the SoA's.  `origin` is filled with the identity again by the next permutation that defers.  Nothing deferred: a compare.
+static int cold_materialise(kid_handle *h) {
+  if (!h->cold.deferred) return KID_OK;
+  KID_HIP(h, hipSetDevice(h->device));
+  { const int rc = rebin_flush_rows(h); if (rc) return rc; }   // (a pending copy composes `origin` once more)
+  h->cold.deferred = false;
+  const kid::ColdSet cs = h->cold.set;
+  h->cold.set = kid::ColdSet{};
+  h->cold.materialised++;
+  PermTable t{};
+  for (int f = 0; f < KID_NB_F64; ++f) if ((cs.f64 >> f) & 1ull) { t.src[t.n8] = h->bp.f[f]; t.dst[t.n8] = h->bp_alt.f[f]; ++t.n8; std::swap(h->bp.f[f], h->bp_alt.f[f]); }
+  if (cs.id) { t.src[t.n8] = h->bp.id; t.dst[t.n8] = h->bp_alt.id; ++t.n8; std::swap(h->bp.id, h->bp_alt.id); }
+  for (int f = 0; f < KID_NB_I32; ++f) if ((cs.i32 >> f) & 1u) { t.src[t.n8 + t.n4] = h->bp.i[f]; t.dst[t.n8 + t.n4] = h->bp_alt.i[f]; ++t.n4; std::swap(h->bp.i[f], h->bp_alt.i[f]); }
+  const long long n = h->n;
+  if (n > 0) hipLaunchKernelGGL(permute_all_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t, (const unsigned *)h->cold.origin, n);
+  KID_HIP(h, hipGetLastError());
+  return berg_table_follows(h);
+}
+// Do the deferred fields still lie outside everything a step of this handle touches?  Asked wherever the answer can change
+// (kid_set_params, kid_set_store_environment, the head of a step, a new re-binning) and by launch_phase for the launch it is about to make
+static bool cold_holds(const kid_handle *h) { return !h->cold.deferred || h->cold.set.within(cold_set(h)); }
+static int cold_settle(kid_handle *h) {
+  if (cold_holds(h)) return KID_OK;
+  const int rc = rebin_flush_rows(h);   // (the pending copy was planned with the deferred set)
+  return rc ? rc : cold_materialise(h);
+}
 // The second set of field arrays and the sort / scan storage of a row permutation, at the first compaction or re-binning
 static int perm_storage(kid_handle *h) {
   if (h->d_key[0]) return KID_OK;
@@ -284,25 +345,46 @@ static int perm_storage(kid_handle *h) {
   for (auto &field : h->bp_alt.f) KID_HIP(h, h->mem.dev(field, (size_t)h->capacity));
   for (auto &field : h->bp_alt.i) KID_HIP(h, h->mem.dev(field, (size_t)h->capacity));
   KID_HIP(h, h->mem.dev(h->bp_alt.id, (size_t)h->capacity));
+  for (int32_t **q : {&h->cold.origin, &h->cold.origin_alt}) KID_HIP(h, h->mem.dev(*q, (size_t)h->capacity));   // cold fields: `origin` and its double
   return KID_OK;
 }
 // The plan of a permutation of n destination rows (perm: the source row of each): the fields that move.  A field that was
 // uploaded as zeros and that no kernel of the configuration writes is zeros before and after, and stays where it is.
-static void perm_fields(kid_handle *h, const unsigned *perm, long long n) {
+// A cold field (kid_rows_plan.hpp) stays where it is as well, whatever it holds, and `origin` moves in its place: one 4-byte
+// field among the int32 ones.  Fields already deferred stay deferred -- the permutation composes `origin` again and never looks
+// at cold data -- and no further field joins them before they are materialised (it would be in row order, they are not).
+// defer_cold = false (compaction: it changes which rows exist, its caller has materialised): every field that is not zeros moves.
+static int perm_fields(kid_handle *h, const unsigned *perm, long long n, bool defer_cold) {
   kid_handle::RebinPlan &pl = h->rplan;
   pl = kid_handle::RebinPlan{};
   PermTable &t = pl.t;
+  kid::ColdSet cold = h->cold.deferred ? h->cold.set : (defer_cold ? cold_set(h) : kid::ColdSet{});
+  if (!h->cold.deferred) {
+    // all zeros, before and after: such a field neither moves nor is deferred (nothing to gather when the rows are read)
+    for (int f = 0; f < KID_NB_F64; ++f) if (!h->zs.uploaded_nonzero[f] && field_never_written(h, f)) cold.f64 &= ~(1ull << f);
+  }
+  if (!h->cold.deferred && !cold.empty()) {
+    hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->cold.origin, (long long)h->n);
+    KID_HIP(h, hipGetLastError());
+    h->cold.deferred = true; h->cold.set = cold;
+  }
   const unsigned long long zeros = known_zero_mask(h);
   for (int f = 0; f < KID_NB_F64; ++f) {
     if (!h->zs.uploaded_nonzero[f] && field_never_written(h, f)) continue;  // all zeros, before and after
     // zeros now, though a later launch may write it (axn, ayn, mass_of_bits): it stays in the array it is in, which is the one
     // every later launch and copy uses.  A fused re-binning launch that no longer knows it as zeros copies first (rebin_take_or_flush)
     if ((zeros >> f) & 1ull) { pl.zero_skipped |= 1ull << f; continue; }
+    if ((cold.f64 >> f) & 1ull) continue;
     t.src[t.n8] = h->bp.f[f]; t.dst[t.n8] = h->bp_alt.f[f]; ++t.n8; pl.moved_f[pl.nmf++] = f; pl.moved |= 1ull << f;
   }
-  t.src[t.n8] = h->bp.id; t.dst[t.n8] = h->bp_alt.id; ++t.n8;
-  for (int f = 0; f < KID_NB_I32; ++f) { t.src[t.n8 + t.n4] = h->bp.i[f]; t.dst[t.n8 + t.n4] = h->bp_alt.i[f]; ++t.n4; }
+  if (!cold.id) { t.src[t.n8] = h->bp.id; t.dst[t.n8] = h->bp_alt.id; ++t.n8; pl.moved_id = true; }
+  for (int f = 0; f < KID_NB_I32; ++f) {
+    if ((cold.i32 >> f) & 1u) continue;
+    t.src[t.n8 + t.n4] = h->bp.i[f]; t.dst[t.n8 + t.n4] = h->bp_alt.i[f]; ++t.n4; pl.moved_i32 |= 1u << f;
+  }
+  if (h->cold.deferred) { t.src[t.n8 + t.n4] = h->cold.origin; t.dst[t.n8 + t.n4] = h->cold.origin_alt; ++t.n4; pl.origin_moves = true; }
   pl.perm = perm; pl.n = n;
+  return KID_OK;
 }
 static const char *const bonds_keep_rows = "bergs with bonds keep their rows: no re-binning while bond tables exist";
 
@@ -328,7 +410,7 @@ int kid_compact_bergs(kid_handle *h) {
   int64_t kept = 0;
   { const int rc = count_rows(h, live, nullptr, &kept); if (rc) return rc; }
   rows_moved(h, false);
-  perm_fields(h, perm, kept);
+  { const int rc = perm_fields(h, perm, kept, false); if (rc) return rc; }
   { const int rc = rebin_apply(h, false, nullptr, nullptr); if (rc) return rc; }
   rows_truncated(h, kept);
   return KID_OK;
@@ -355,7 +437,9 @@ static bool rebin_fusable(const kid_handle *h) {
 int kid_move_berg_between_cells(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc_h = halo_rows_refuse(h, "kid_move_berg_between_cells"); if (rc_h) return rc_h; }
-  { const int rc_e = rows_enter(h, ROWS_CHANGE); if (rc_e) return rc_e; }   // (re-binning twice in a row: the second one sorts the rows of the first)
+  // (re-binning twice in a row: the second one sorts the rows of the first.)  Cold fields stay deferred: only `origin` is composed again
+  { const int rc_e = rows_enter(h, ROWS_CHANGE, COLD_LEAVE); if (rc_e) return rc_e; }
+  { const int rc_c = cold_settle(h); if (rc_c) return rc_c; }
   h->steps_since_sort = 0;
   if (h->n == 0) return KID_OK;
   if (h->have_bonds) { h->err = bonds_keep_rows; return KID_EUNSUPPORTED; }
@@ -401,22 +485,17 @@ static int rebin_plan(kid_handle *h, bool dead_last) {
     perm = h->d_idx[1];
     if (carry_repro) { hipLaunchKernelGGL(translate_rows_kernel, dim3(nb), dim3(256), 0, h->stream, h->rp.srows, (const unsigned *)h->d_idx[0], n); h->rp.srows_n = n; }
   }
-  perm_fields(h, perm, n);
   KID_HIP(h, hipGetLastError());
-  return KID_OK;
+  return perm_fields(h, perm, n, true);
 }
 // the planned rows change places on the host: the second set of arrays becomes the SoA; the device's pointer table follows
 static int rebin_swap(kid_handle *h) {
   const kid_handle::RebinPlan &pl = h->rplan;
   for (int q = 0; q < pl.nmf; ++q) std::swap(h->bp.f[pl.moved_f[q]], h->bp_alt.f[pl.moved_f[q]]);
-  std::swap(h->bp.id, h->bp_alt.id);
-  for (int f = 0; f < KID_NB_I32; ++f) std::swap(h->bp.i[f], h->bp_alt.i[f]);
-  if (h->tables_dirty) return refresh_tables(h);
-  // only the field pointers changed: one table, not four (a launch on the side stream may still be reading it)
-  { const int rc = join_side(h); if (rc) return rc; }
-  hipLaunchKernelGGL(set_berg_table_kernel, dim3(1), dim3(64), 0, h->stream, h->bp, h->d_bp);
-  KID_HIP(h, hipGetLastError());
-  return KID_OK;
+  if (pl.moved_id) std::swap(h->bp.id, h->bp_alt.id);
+  for (int f = 0; f < KID_NB_I32; ++f) if ((pl.moved_i32 >> f) & 1u) std::swap(h->bp.i[f], h->bp_alt.i[f]);
+  if (pl.origin_moves) std::swap(h->cold.origin, h->cold.origin_alt);
+  return berg_table_follows(h);
 }
 // apply: ONE launch gathers every moving field into the second set of arrays
 static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count) {
@@ -436,11 +515,15 @@ static int rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list
   KID_HIP(h, hipGetLastError());
   return rebin_swap(h);
 }
-static int rebin_flush(kid_handle *h) {
+static int rebin_flush_rows(kid_handle *h) {
   if (!h->rebin_pending) return KID_OK;
   h->rebin_pending = false;
   KID_HIP(h, hipSetDevice(h->device));
   return rebin_apply(h, false, nullptr, nullptr);
+}
+static int rebin_flush(kid_handle *h) {
+  const int rc = rebin_flush_rows(h);
+  return rc ? rc : cold_materialise(h);
 }
 // The table of the re-binning instance of the plain hot build K for the pending plan.  The moved fields that build does not
 // write itself are head copies (KID_RB_NX8 with the id; the int32 fields always fit); what is left over is `surplus`.
@@ -449,22 +532,30 @@ static bool rebin_table(const kid_handle *h, int K, RebinTab &tab) {
   tab = RebinTab{};
   tab.dst = h->bp;
   for (int q = 0; q < pl.nmf; ++q) tab.dst.f[pl.moved_f[q]] = h->bp_alt.f[pl.moved_f[q]];
-  tab.dst.id = h->bp_alt.id;
-  for (int f = 0; f < KID_NB_I32; ++f) tab.dst.i[f] = h->bp_alt.i[f];
+  if (pl.moved_id) tab.dst.id = h->bp_alt.id;
+  for (int f = 0; f < KID_NB_I32; ++f) if ((pl.moved_i32 >> f) & 1u) tab.dst.i[f] = h->bp_alt.i[f];
   tab.moved = pl.moved;
+  const int id_slot = pl.moved_id ? 1 : 0;
   const unsigned long long own = KID_RB_DYN | rb_thermo_fields(K);
   for (int q = 0; q < pl.nmf; ++q) {
     const int f = pl.moved_f[q];
     if ((own >> f) & 1ull) continue;
-    if (tab.n8 >= KID_RB_NX8 - 1) { tab.surplus |= 1ull << f; continue; }
+    if (tab.n8 >= KID_RB_NX8 - id_slot) { tab.surplus |= 1ull << f; continue; }
     tab.xs[tab.n8] = h->bp.f[f]; tab.xd[tab.n8] = h->bp_alt.f[f]; ++tab.n8;
   }
-  tab.xs[tab.n8] = h->bp.id; tab.xd[tab.n8] = h->bp_alt.id; ++tab.n8;
+  if (pl.moved_id) { tab.xs[tab.n8] = h->bp.id; tab.xd[tab.n8] = h->bp_alt.id; ++tab.n8; }
+  // every moving int32 field but the cell is a head copy, and so is `origin` when cold fields are deferred: the cold int32
+  // fields (at least conglom_id) have left the head copies then, so the four slots still hold them
   static_assert(KID_NB_I32 - 2 <= KID_RB_NX4, "every int32 field but the cell is a head copy");
+  static_assert((kid::cold_set(kid::ColdIn{true, true, true, true, true, true, true}).i32 & ~(1u << KID_BI_INE | 1u << KID_BI_JNE)) != 0u, "a cold int32 field makes room for origin");
+  int n4 = 0;
+  for (int f = 0; f < KID_NB_I32; ++f) if (f != KID_BI_INE && f != KID_BI_JNE && ((pl.moved_i32 >> f) & 1u)) ++n4;
+  if (n4 + (pl.origin_moves ? 1 : 0) > KID_RB_NX4) return false;   // (the caller copies first)
   for (int f = 0; f < KID_NB_I32; ++f) {
-    if (f == KID_BI_INE || f == KID_BI_JNE) continue;
+    if (f == KID_BI_INE || f == KID_BI_JNE || !((pl.moved_i32 >> f) & 1u)) continue;
     tab.xs[KID_RB_NX8 + tab.n4] = h->bp.i[f]; tab.xd[KID_RB_NX8 + tab.n4] = h->bp_alt.i[f]; ++tab.n4;
   }
+  if (pl.origin_moves) { tab.xs[KID_RB_NX8 + tab.n4] = h->cold.origin; tab.xd[KID_RB_NX8 + tab.n4] = h->cold.origin_alt; ++tab.n4; }
   return true;
 }
 int kid_set_resort_interval(kid_handle *h, int steps) {
@@ -477,6 +568,14 @@ int kid_set_resort_interval(kid_handle *h, int steps) {
 int kid_perm_moved_fields(kid_handle *h, int64_t *count) {
   if (!h || !count) return KID_EINVAL;
   *count = h->rplan.nmf;
+  return KID_OK;
+}
+// Cold fields: are any deferred behind a permutation now, and how many times have they been gathered into row order so far?
+// A hook for tests/test_cold_rows_gpu.py like the one above; it looks at the handle only and moves nothing.
+int kid_cold_state(kid_handle *h, int32_t *deferred, int64_t *materialised_count) {
+  if (!h) return KID_EINVAL;
+  if (deferred) *deferred = h->cold.deferred ? 1 : 0;
+  if (materialised_count) *materialised_count = h->cold.materialised;
   return KID_OK;
 }
 

@@ -118,4 +118,72 @@ constexpr unsigned long long known_zero_mask(const ZeroState &z, bool heat_densi
   return m;
 }
 
+// Cold fields: the members no kernel of a step the handle can currently run reads or writes by row.  A row permutation leaves
+// them in the array they are in and moves one int32 per row instead, `origin`: field f of row k is cold[f][origin[k]] until a
+// reader asks for the rows (kid_rows.inc, cold_materialise).  Only a handle whose step is one plain fused launch defers
+// anything (`fusable`: rebin_fusable of kid_rows.inc -- RK4, old interpolation order, no mts / interactions / footloose /
+// static_icebergs / find_melt_using_spread_mass, plain namelist): its step is berg_kernel<RK, OLD, PH_STEP> as hot build
+// (K = 1 or 3) and as general build (K = 0), the forcing prepass and the gather, and of these only berg_kernel looks at rows.
+// step_touches_* follows that kernel (kid_berg_kernel.hpp) load by load and store by store; a member it does not know is touched.
+// The guard that decides today is `fusable`: it implies the plain namelist (diag_mask 0, iceberg_bonds_on 0, RK4) and neither
+// has_static nor has_fl, so of the conditions below only periodic_reentry can take its other value on a handle that defers
+// anything; the rest are what the kernel's own conditions say, kept so that a wider `fusable` cannot make a field cold that the
+// step then reads.  tests/cold_rows_host.cpp enumerates the rule (against its statement in words, not against the kernel) and
+// the composition of `origin`.
+struct ColdIn { bool fusable, runge_not_verlet, periodic_reentry, has_static, has_fl, bonds_on, melt_by_class; };
+constexpr bool step_touches_f64(const ColdIn &s, int f) {
+  switch (f) {
+    case KID_B_START_LON: case KID_B_START_LAT:   // no load, no store
+    case KID_B_AXN_FAST: case KID_B_AYN_FAST: case KID_B_BXN_FAST: case KID_B_BYN_FAST: case KID_B_ANG_VEL: case KID_B_ANG_ACCEL: case KID_B_ROT:   // the MTS / DEM kernels only
+      return false;
+    case KID_B_UVEL_PREV: case KID_B_VVEL_PREV:
+      return !s.runge_not_verlet;   // stored by the Verlet evolve
+    case KID_B_UVEL_OLD: case KID_B_VVEL_OLD: case KID_B_LON_OLD: case KID_B_LAT_OLD:
+      return s.periodic_reentry;    // stored for a berg that re-enters across the seam (general build)
+    case KID_B_HALO_BERG: case KID_B_STATIC_BERG:
+      return s.has_static;          // loaded at the head of the kernel under Flags::has_static
+    case KID_B_MASS_OF_FL_BITS: case KID_B_MASS_OF_FL_BERGY_BITS: case KID_B_FL_K:
+    case KID_B_START_DAY:           // stored when a berg turns into a footloose child
+      return s.has_fl;
+    case KID_B_START_MASS:
+      return s.melt_by_class;       // loaded for the melt-by-class diagnostic
+    default:
+      return true;                  // position, velocity, accelerations, size, mass_scaling, bits, heat density, the environment
+  }
+}
+constexpr bool step_touches_i32(const ColdIn &s, int f) {
+  switch (f) {
+    case KID_BI_START_YEAR: return s.has_fl;     // stored with start_day
+    case KID_BI_N_BONDS: return s.bonds_on;      // loaded under iceberg_bonds_on
+    case KID_BI_CONGLOM_ID: return false;
+    default: return true;                        // the cell, alive
+  }
+}
+static_assert(KID_NB_I32 <= 32, "one bit per int32 field");
+struct ColdSet {
+  unsigned long long f64 = 0ull; unsigned i32 = 0u; bool id = false;
+  constexpr bool empty() const { return f64 == 0ull && i32 == 0u && !id; }
+  constexpr bool within(const ColdSet &o) const { return (f64 & ~o.f64) == 0ull && (i32 & ~o.i32) == 0u && (!id || o.id); }
+  constexpr int bytes_per_row() const {
+    int b = id ? 8 : 0;
+    for (int f = 0; f < KID_NB_F64; ++f) b += ((f64 >> f) & 1ull) ? 8 : 0;
+    for (int f = 0; f < KID_NB_I32; ++f) b += ((i32 >> f) & 1u) ? 4 : 0;
+    return b;
+  }
+};
+// the id is never looked at by the step
+constexpr ColdSet cold_set(const ColdIn &s) {
+  ColdSet c;
+  if (!s.fusable) return c;
+  for (int f = 0; f < KID_NB_F64; ++f) if (!step_touches_f64(s, f)) c.f64 |= 1ull << f;
+  for (int f = 0; f < KID_NB_I32; ++f) if (!step_touches_i32(s, f)) c.i32 |= 1u << f;
+  c.id = true;
+  return c;
+}
+// `origin` through a permutation (perm[k]: the source row of destination row k): what permute_all_kernel and the re-binning
+// instance do to it as one more 4-byte field.  Composing again never looks at cold data.
+constexpr void origin_compose(const int32_t *origin_src, const unsigned *perm, long long n, int32_t *origin_dst) {
+  for (long long k = 0; k < n; ++k) origin_dst[k] = origin_src[perm[k]];
+}
+
 }  // namespace kid

@@ -723,6 +723,13 @@ class Icebergs:
         self._check(self.lib.kid_hot_zero_mask(self.h, C.byref(m)), "kid_hot_zero_mask")
         return {name for f, name in enumerate(T.BERG_F64_NAMES) if (m.value >> f) & 1}
 
+    def cold_state(self):
+        """(deferred, materialised): are cold fields waiting behind a row permutation now, and how many times have they been
+        gathered into row order so far (kid_cold_state, a hook for tests; nothing deferred ever with KID_COLD_EAGER=1)"""
+        d, m = C.c_int32(), C.c_int64()
+        self._check(self.lib.kid_cold_state(self.h, C.byref(d), C.byref(m)), "kid_cold_state")
+        return bool(d.value), m.value
+
     def profile(self, on=True):
         self._check(self.lib.kid_profile_enable(self.h, 1 if on else 0), "kid_profile_enable")
 
