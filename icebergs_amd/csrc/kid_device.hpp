@@ -88,9 +88,16 @@ template <int K> struct Sw {
 };
 
 // Division and square root.  The IEEE expansions cost ~12 (division) and ~16 (square root) instructions each, a fifth of
-// the hot build.  Unless -DKID_EXACT_MATH, a quotient is a product with a Newton-refined v_rcp_f64 (error <= ~1.5 ulp
+// the hot build.  Unless -DKID_EXACT_MATH, a quotient is a product with a Newton-refined v_rcp_f64 (error <= 1.5 ulp
 // instead of 0.5), so that divisors which repeat (M, the cell area, dt, W+L, ...) are inverted once; results then differ
 // from the oracle's at the 1e-16 level (tolerance 1e-10), like the other trims.
+// Every bound below is asserted of the device code by tests/test_device_math_gpu.py and, for any seed within 2^-23 of the
+// reciprocal (what the ISA specifies for v_rcp_f64 and v_rsq_f64), of the iterations themselves by tests/test_device_math_cpu.py;
+// DESIGN.md section 4 keeps the measured figures and the table of call sites.
+// Domain: a finite divisor with 2^-1022 <= |b| <= 2^1022, and a finite numerator for kid_div / kid_div_r.  Outside it the forms
+// do NOT follow IEEE: b = +-0 or +-inf gives NaN (IEEE: inf, 0) because the residual fma(-b, r, 1) of (0, inf) is NaN; a denormal
+// divisor whose reciprocal overflows (5e-324, 2^-1030) gives NaN where IEEE gives inf (the seed is inf); kid_div(+-inf, b) is NaN (its residual is inf - inf) where a * Rcp is IEEE's
+// inf.  A NaN operand gives NaN.  No call site reaches these with a result the reference would have kept finite.
 #ifdef KID_EXACT_MATH
 struct Rcp { double d; };
 __device__ __forceinline__ Rcp kid_rcp(double b) { return Rcp{b}; }
@@ -99,7 +106,7 @@ __device__ __forceinline__ double kid_div(double a, double b) { return a / b; }
 #else
 struct Rcp { double r; };
 __device__ __forceinline__ Rcp kid_rcp(double b) {
-  double r = __builtin_amdgcn_rcp(b);          // ~2^-26 relative
+  double r = __builtin_amdgcn_rcp(b);          // ~2^-26 relative (specified: 2^-23)
   double e = __builtin_fma(-b, r, 1.0);
   r = __builtin_fma(r, e, r);
   e = __builtin_fma(-b, r, 1.0);
@@ -107,7 +114,9 @@ __device__ __forceinline__ Rcp kid_rcp(double b) {
   return Rcp{r};
 }
 __device__ __forceinline__ double operator*(double a, Rcp r) { return a * r.r; }
-__device__ __forceinline__ double kid_div(double a, double b) {  // one more correction: <= ~0.6 ulp
+// one more correction: <= 0.6 ulp (the last fma rounds q + (a - b q) r, which is a / b to ~2^-100: correctly rounded on every
+// input the tests sweep).  kid_div(a, b) >= 1 whenever a >= b > 0, and == 1 for a == b: accel's cr_q leans on it.
+__device__ __forceinline__ double kid_div(double a, double b) {
   const Rcp r = kid_rcp(b);
   const double q = a * r.r;
   return __builtin_fma(__builtin_fma(-b, q, a), r.r, q);
@@ -133,7 +142,11 @@ __device__ __forceinline__ double kid_fma(double a, double b, double c) { return
 #endif
 // Square root of a speed or a length: one Goldschmidt step on v_rsq_f64 (~23 bits) and one residual correction, <= 1 ulp;
 // without the range scaling of the IEEE expansion (the arguments are sums of squares of velocities, areas, ...: far from the
-// ends of the exponent range) -- 11 instructions instead of 17.  0 and negative arguments as sqrt() treats them.
+// ends of the exponent range) -- 11 instructions instead of 17.  +-0, +inf, negative arguments and NaN as sqrt() treats them.
+// The 1 ulp holds for 1e-300 <= x <= the largest double.  Below, the residual x - g^2 (~x 2^-44) is a denormal, rounded to a
+// multiple of 2^-1074: the bound becomes 1 + 2^-1023 / x ulp (2 ulp at 2^-1023, measured 2.6 ulp over the denormals) -- still a
+// root, never NaN.  A caller's largest argument is a squared speed or length (< 1e16), its smallest non-zero one a squared
+// difference of speeds of ~1e-32.
 #ifdef KID_EXACT_MATH
 __device__ __forceinline__ double kid_sqrt(double x) { return sqrt(x); }
 #else
@@ -143,7 +156,8 @@ __device__ __forceinline__ double kid_sqrt(double x) {
   const double r = __builtin_fma(-h, g, 0.5);
   g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
   g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
-  return (x > 0.) ? g : ((x == 0.) ? x : __builtin_nan(""));
+  // x > 0 and finite: the iteration; +-0 and +inf: x itself (the iteration makes inf * 0 = NaN of +inf); negative, NaN: NaN
+  return __builtin_amdgcn_class(x, 0x180) ? g : (__builtin_amdgcn_class(x, 0x260) ? x : __builtin_nan(""));
 }
 #endif
 
@@ -155,7 +169,10 @@ template <bool IEEE> __device__ __forceinline__ double kid_div_t(double a, doubl
 
 // The same for a sum of squares of speeds (never negative, never infinite): the seed is taken of max(x, 1e-300), so x = 0 comes
 // out as 0 through the arithmetic itself (g = 0 * 1e150 = 0 in every step) and the three selects of the general form go; the
-// result is the same bits as kid_sqrt(x) for every x that is 0 or >= 1e-300.
+// result is the same bits as kid_sqrt(x) for every x that is 0 or >= 1e-300.  For 0 < x < 1e-300 (a speed below 1e-150 m/s) it
+// is NOT the root but some number in [0, 2.25e-150] (g0 = x y < 1e-150 with y = rsq(1e-300), one step takes it to <= 1.5 g0 and
+// the correction adds <= x * 0.75 y): a drag coefficient times that is the 0 the exact root's 1e-150 would have given as well.
+// A negative or NaN argument gives NaN or a wrong number, +inf gives NaN: no caller forms one.
 #ifdef KID_EXACT_MATH
 __device__ __forceinline__ double kid_sqrt_nn(double x) { return sqrt(x); }
 #else
@@ -168,7 +185,8 @@ __device__ __forceinline__ double kid_sqrt_nn(double x) {
 }
 #endif
 
-// 1/sqrt(x), x > 0 finite: v_rsq_f64 (~23 bits) and two Newton steps y <- y + y (1 - x y^2) / 2, <= 1 ulp
+// 1/sqrt(x), x > 0 finite: v_rsq_f64 (~23 bits) and two Newton steps y <- y + y (1 - x y^2) / 2, <= 1 ulp for 1e-300 <= x <= 1e300
+// (the rounded product x y puts <= 2^-53 absolute into the residual, half of it reaches y: 0.5 ulp, and the last fma rounds once)
 #ifndef KID_EXACT_MATH
 __device__ __forceinline__ double kid_rsqrt(double x) {
   double y = __builtin_amdgcn_rsq(x);
@@ -178,6 +196,13 @@ __device__ __forceinline__ double kid_rsqrt(double x) {
   return __builtin_fma(y, 0.5 * e, y);
 }
 #endif
+
+// sin(x) of a bond's relative rotation (kid_mts.inc), |x| < 0.25: x - x^3/3! + ... - x^15/15! as nested products, truncation
+// 0.25^17/17! < 1e-24; the rounded products and differences of the chain leave <= 1 ulp (tests/test_device_math_gpu.py)
+__device__ __forceinline__ double kid_sin_series15(double x) {
+  const double x2 = x * x;
+  return x * (1. - x2 * (1. / 6.) * (1. - x2 * (1. / 20.) * (1. - x2 * (1. / 42.) * (1. - x2 * (1. / 72.) * (1. - x2 * (1. / 110.) * (1. - x2 * (1. / 156.) * (1. - x2 * (1. / 210.))))))));
+}
 
 // reference module constants, IB:68-80
 constexpr double RHO_ICE = 916.7, RHO_AIR = 1.1, RHO_SEAWATER = 1025.0, GRAVITY = 9.8;
@@ -711,14 +736,17 @@ __device__ __forceinline__ void accel(const DevGrid &g, const kid_params &p, con
 #else
   // min(max(0, q), 1) of q = (L - Lcutoff) / (Ltop - Lcutoff + 1e-30) is 1 exactly when the numerator is not below the
   // denominator -- any berg longer than a quarter of the wave length, i.e. nearly all of them: the division is done only in waves
-  // that hold a shorter one (each lane's value is the same either way)
+  // that hold a shorter one.  Each lane's value is the same either way: kid_div(a, b) >= 1 whenever a >= b > 0 -- its last fma rounds
+  // a number within 2^-100 of a / b >= 1, and everything above 1 - 2^-54 rounds to 1 or more (tests/test_device_math_gpu.py asserts
+  // it of the device, tests/test_wave_mix_gpu.py runs bergs on that edge in waves with and without a shorter one)
   const double cr_num = ap.L - Lcutoff, cr_den = (Ltop - Lcutoff) + 1.e-30;
   double cr_q = 1.;
   if (__ballot(!(cr_num >= cr_den)) != 0ull) cr_q = dmin(dmax(0., kid_div(cr_num, cr_den)), 1.);
   const double Cr = 0.06 * cr_q;
   const double wave_rad = ap.wave_q * Cr * ampl * dmin(ampl, ap.F);
   // the unit vector of the wind from one Newton-refined reciprocal square root.  No wind: ua = va = 0, and 0 times the (finite)
-  // root of the floor is the reference's uwave = vwave = 0; its wave_rad = 0 only ever multiplies them
+  // root of the floor is the reference's uwave = vwave = 0; its wave_rad = 0 only ever multiplies them.  A wind below 1e-150 m/s
+  // (wmod < 1e-300) gives a vector shorter than the reference's unit vector; wave_rad, proportional to wmod^2, has underflowed to 0
   wmod = kid_fma(ua, ua, va * va);
   { const double rw = kid_rsqrt(__builtin_fmax(wmod, 1.e-300)); uwave = ua * rw; vwave = va * rw; }
 #endif
@@ -907,6 +935,11 @@ __device__ __forceinline__ LatTerms lat_terms(const DevGrid &g, const kid_params
 // (|d| < 0.02 rad: truncation < 1e-18) -- ~15 instructions instead of a sincos with argument reduction
 // (~120, 6 % of the step's vector instructions).  Both builds use it (the same numbers for a berg whichever build steps
 // it); not bitwise equal to sincos(lat) (differences ~2e-16); -DKID_EXACT_MATH keeps sincos.
+// Absolute error of s and c against sin / cos of the double lat * pi_180: <= 1e-15 (three roundings of ~1.1e-16 -- the table
+// entry, cd, the final fma -- up to ~3.3e-16 from the rounding of the angle and of d, truncation < 1e-17), for lat_c up to the
+// pole; c > 0 for every |lat| < 90 (the measured error, 2e-16, is below the 3e-16 that cos is one ulp short of the pole; asserted
+// for the last 39 doubles below +-90 from lat_c = +-89 and +-89.99), so the divisor Rearth * c of dxdl is never 0 (at the pole
+// itself cos is 6.1e-17, not 0).
 template <int K = 0>
 __device__ __forceinline__ LatTerms lat_terms_cell(const DevGrid &g, const kid_params &p, double lat, double sin_ref,
                                                    double lat_c, double s_c, double c_c, bool have_ref) {
@@ -959,14 +992,17 @@ __device__ __forceinline__ LatTerms lat_terms_near(const DevGrid &g, const kid_p
 }
 
 // footloose beam constants (IB:2538-2547, 3013-3015, 3376-3378): 1/(g rho_sw) and 1/(12 (1 - 0.3**2)) are literals of the
-// source, folded at compile time with the same IEEE operations; x**3 and x**0.25 of the buoyancy length are x*x*x and
-// sqrt(sqrt(x)) (within an ulp of pow; -DKID_EXACT_MATH keeps pow)
+// source, folded at compile time with the same IEEE operations; x**3 and x**0.25 of the buoyancy length are x*x*x with the
+// rounding error of x*x carried along (e = fma(x, x, -x2) is that error exactly, x^3 = x2 x + e x: one rounding, <= 0.51 ulp;
+// the plain product (x*x)*x measured 1.22 ulp) and sqrt(sqrt(x)) (two correctly rounded roots: the inner one's half ulp is halved
+// by the outer root, <= 1 ulp, measured 0.82); both within an ulp of the exact power for 1e-90 <= x <= 1e90, what
+// tests/test_device_math_gpu.py sweeps (a thickness or a length in metres is far inside); -DKID_EXACT_MATH keeps pow
 constexpr double FL_LW_C = 1. / (GRAVITY * RHO_SEAWATER), FL_B_C1 = 1. / (12. * (1. - 0.3 * 0.3));
 #ifdef KID_EXACT_MATH
 __device__ __forceinline__ double kid_cube(double x) { return pow(x, 3.); }
 __device__ __forceinline__ double kid_root4(double x) { return pow(x, 0.25); }
 #else
-__device__ __forceinline__ double kid_cube(double x) { return x * x * x; }
+__device__ __forceinline__ double kid_cube(double x) { const double x2 = x * x; return __builtin_fma(x2, x, __builtin_fma(x, x, -x2) * x); }
 __device__ __forceinline__ double kid_root4(double x) { return sqrt(sqrt(x)); }
 #endif
 

@@ -1099,10 +1099,7 @@ __global__ void __launch_bounds__(MTS_FUSED_BS) mts_substeps_kernel(const DevGri
       for (int s = 0; s < MB; ++s) small = small && (fabs(mid[s].arg) < 0.25);
       if (__ballot(!small) == 0ull) {
 #pragma unroll
-        for (int s = 0; s < MB; ++s) {   // x - x^3/3! + ... - x^15/15!: truncation 0.25^17/17! < 1e-24
-          const double x = mid[s].arg, x2 = x * x;
-          th[s] = x * (1. - x2 * (1. / 6.) * (1. - x2 * (1. / 20.) * (1. - x2 * (1. / 42.) * (1. - x2 * (1. / 72.) * (1. - x2 * (1. / 110.) * (1. - x2 * (1. / 156.) * (1. - x2 * (1. / 210.))))))));
-        }
+        for (int s = 0; s < MB; ++s) th[s] = kid_sin_series15(mid[s].arg);   // x - x^3/3! + ... - x^15/15!
       } else {
 #pragma unroll
         for (int s = 0; s < MB; ++s) th[s] = pair_theta(p, mid[s].arg);

@@ -193,8 +193,9 @@ __device__ __forceinline__ void seg_flush(StageSeg &, double *, size_t) {}
 
 // one out-of-line copy of ocml's pow (about 3 KB of code per inlined call site)
 __device__ __noinline__ double kid_pow(double x, double y) { return pow(x, y); }
-// x**y for the melt laws (x >= 0, y in {0.2, 0.8}): exp(y*log(x)) is within ~2e-15 relative of the correctly rounded pow
-// (|y*log x| < 8 here) at half its instruction count; -DKID_EXACT_MATH keeps ocml's pow
+// x**y for the melt laws (x >= 0, y in {0.2, 0.8}): exp(y*log(x)) is within 2e-15 relative of the exact power
+// (|y*log x| < 8 here; in general (1.5 |y log x| + 1) 2^-52: the rounding of the exponent's argument grows with it) at half
+// pow's instruction count; -DKID_EXACT_MATH keeps ocml's pow
 #ifdef KID_EXACT_MATH
 __device__ __forceinline__ double kid_powr(double x, double y) { return kid_pow(x, y); }
 #else
@@ -203,9 +204,13 @@ __device__ __noinline__ double kid_powr(double x, double y) { return (x == 0.) ?
 // The melt laws' x**0.8 and a / x**0.2 (IB:2912, 2914, 3046, 3084, 3100).  Both come from r = x**(-1/5): a single-precision seed
 // (v_log_f32, v_exp_f32: ~1e-6 relative) and two Newton steps r <- r + r (1 - x r^5) / 5 -- no division, the error goes
 // 1e-6 -> 3e-12 -> 3e-23 (checked against 50-digit arithmetic with the seed off by 3e-6: 3e-16 after the second step, the
-// rounding of the steps themselves; round 2 ran a third) -- ~20 instructions against ~150 for exp(y log x) + a division;
-// x**0.8 = x r.  Within ~1 ulp of pow.
-// Outside the seed's range (and for 0, inf, NaN) the general form; -DKID_EXACT_MATH keeps pow.
+// rounding of the steps themselves) -- ~20 instructions against ~150 for exp(y log x) + a division;
+// x**0.8 = x r.  r itself is within 1 ulp of x**(-1/5) on (1e-30, 1e30) for any seed within 3e-6; the products x r and a r
+// carry r's error into a second rounding: <= 2.3 ulp of the exact x**0.8 and a / x**0.2 (derived in tests/device_math_sets.py:
+// the three rounded products of r^5 put <= 4 u into the residual, 0.8 u into r, 1.8 u with r's own rounding; measured 1.83 and
+// 1.59 ulp).
+// Outside the seed's range (and for 0, inf, NaN, which come out as pow gives them) the general form, within kid_powr's bound;
+// -DKID_EXACT_MATH keeps pow.
 #ifdef KID_EXACT_MATH
 __device__ __forceinline__ double kid_mul_rpow5(double a, double x) { return a / kid_pow(x, 0.2); }
 __device__ __forceinline__ double kid_pow08(double x) { return kid_pow(x, 0.8); }
