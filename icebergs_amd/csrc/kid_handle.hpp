@@ -147,6 +147,7 @@ struct kid_handle {
   bool use_graph = true;
   int fused_blocks[2] = {0, 0};             // co-resident workgroups of mts_substeps_kernel<4> / <8> (0: not asked yet)
   bool fused_ran = false;                   // a fused sub-step launch since the last look at its time-out counter
+  int64_t fused_launches = 0;               // fused sub-step launches since kid_create (kid_mts_fused_launches: tests)
   Flags flags{0, 0, 1, 0, 0};
   // trajectories (kid_traj.inc): one buffer per sampled field, grown on demand
   bool traj_on = false; kid_traj_params traj_params{}; double *d_traj_f[64] = {}; double *d_traj_day = nullptr; int64_t *d_traj_id = nullptr;

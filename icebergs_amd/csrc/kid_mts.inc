@@ -378,6 +378,9 @@ __device__ __forceinline__ PairOut pair_force_dem(const DevGrid &g, const kid_pa
   return pair_finish(p, c, q, pair_theta(p, q.arg));
 }
 
+__device__ __forceinline__ bool mts_active(const BergPtrs &b, long long k) {
+  return MI(KID_BI_ALIVE, k) != 0 && MF(KID_B_STATIC_BERG, k) < 0.5 && MI(KID_BI_CONGLOM_ID, k) != 0;
+}
 // (savestress, save_bond_forces): the primary side (k,s) evaluates the pair and writes both records
 __device__ __forceinline__ void calculate_force_dem(const DevGrid &g, const kid_params &p, const BergPtrs &b, const MtsDev &m, long long k, int s, double dt) {
   const int o = m.bother_row[MB_S(s, k)];
@@ -411,15 +414,11 @@ __device__ __forceinline__ void calculate_force_dem(const DevGrid &g, const kid_
     double nb = 1.;
     if (p.use_broken_bonds_for_substep_contact) atomicSub(&MI(KID_BI_N_BONDS, k), 1);
     if (so >= 0) {
-      m.bbroken[MB_S(so, o)] = 3; nb = 2.;
+      m.bbroken[MB_S(so, o)] = mts_active(b, o) ? 3 : 1; nb = 2.;   // a partner that is not swept never consumes the forces: broken at once, as the reference leaves it
       if (p.use_broken_bonds_for_substep_contact) atomicSub(&MI(KID_BI_N_BONDS, o), 1);
     }
     unsafeAtomicAdd(m.red + MR_NBROKEN, nb);
   }
-}
-
-__device__ __forceinline__ bool mts_active(const BergPtrs &b, long long k) {
-  return MI(KID_BI_ALIVE, k) != 0 && MF(KID_B_STATIC_BERG, k) < 0.5 && MI(KID_BI_CONGLOM_ID, k) != 0;
 }
 
 // one lane per bond slot (slot-major: a wave holds one slot of 64 consecutive bergs, so the slot-major tables are read
@@ -1096,7 +1095,8 @@ __global__ void __launch_bounds__(MTS_FUSED_BS) mts_substeps_kernel(const DevGri
       small = false;
 #endif
 #pragma unroll
-      for (int s = 0; s < MB; ++s) small = small && (fabs(mid[s].arg) < 0.25);
+      for (int s = 0; s < MB; ++s) small = small && (!(in && pair[s]) || fabs(mid[s].arg) < 0.25);   // only slots that count: a slot without a partner, or a lane
+                                                                                                      // past the last berg, reads a record nobody waited for (the empty mark is a NaN)
       if (__ballot(!small) == 0ull) {
 #pragma unroll
         for (int s = 0; s < MB; ++s) th[s] = kid_sin_series15(mid[s].arg);   // x - x^3/3! + ... - x^15/15!
@@ -1134,9 +1134,9 @@ __global__ void __launch_bounds__(MTS_FUSED_BS) mts_substeps_kernel(const DevGri
             MBD(KID_BOND_F_X, s, kk) = fx; MBD(KID_BOND_F_Y, s, kk) = fy; MBD(KID_BOND_FD_X, s, kk) = fdx; MBD(KID_BOND_FD_Y, s, kk) = fdy;
             MBD(KID_BOND_T, s, kk) = tq; MBD(KID_BOND_T_D, s, kk) = tdq;
           }
-          if (r.broke) {   // each side marks its own record (a berg that is not swept keeps the mark 3, as in bond_pass_kernel)
+          if (r.broke) {   // each side marks its own record (1 also on a berg that is not swept, as in calculate_force_dem: labelling and downloads see the reference's mark)
             fresh |= 1 << s;
-            br[s] = act_k ? 1 : 3;
+            br[s] = 1;
             m.bbroken[MB_S(s, kk)] = br[s];
             m.red[MR_BREAK] = 1.;
             if (p.use_broken_bonds_for_substep_contact) atomicSub(&MI(KID_BI_N_BONDS, kk), 1);

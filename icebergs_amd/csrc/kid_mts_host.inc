@@ -361,11 +361,19 @@ static int mts_fused_substeps(kid_handle *h, bool &enqueued) {
   int poll_arg = h->dbg.mts_poll_limit > 0 ? h->dbg.mts_poll_limit : (int)MTS_POLL_LIMIT; int *to_arg = h->d_order_flag + 2;
   void *args[] = {&g_arg, &pp_arg, &bt_arg, &mt_arg, &n_arg, &nsub_arg, &poll_arg, &to_arg};
   const hipError_t e = hipLaunchCooperativeKernel(fn, dim3((unsigned)need_blocks), dim3(MTS_FUSED_BS), args, 0, h->stream);
-  if (e == hipSuccess) { h->fused_ran = true; return KID_OK; }
+  if (e == hipSuccess) { h->fused_ran = true; h->fused_launches++; return KID_OK; }
   if (e != hipErrorCooperativeLaunchTooLarge) { h->err = std::string("hipLaunchCooperativeKernel: ") + hipGetErrorString(e); return KID_EHIP; }
   (void)hipGetLastError();
   fused_blocks = std::max(1, fused_blocks / 2);
   return mts_plain_substeps(h, 1, h->params.mts_sub_steps, true, false, false);
+}
+
+// How many times has the sub-step loop of this handle gone out as the one cooperative launch (mts_substeps_kernel) so far?  A hook
+// for tests/test_dem_rows_gpu.py, not part of include/kid.h: a case about the fused loop must not pass on the three-launch fall-back.
+int kid_mts_fused_launches(kid_handle *h, int64_t *count) {
+  if (!h || !count) return KID_EINVAL;
+  *count = h->fused_launches;
+  return KID_OK;
 }
 
 // evolve_icebergs_mts (IB:6576-7078)

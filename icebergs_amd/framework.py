@@ -730,6 +730,13 @@ class Icebergs:
         self._check(self.lib.kid_cold_state(self.h, C.byref(d), C.byref(m)), "kid_cold_state")
         return bool(d.value), m.value
 
+    def mts_fused_launches(self):
+        """how many times the MTS sub-step loop went out as the one cooperative launch so far (kid_mts_fused_launches, a hook
+        for tests; stays 0 with KID_MTS_NO_FUSED=1 or when the population does not fit)"""
+        c = C.c_int64()
+        self._check(self.lib.kid_mts_fused_launches(self.h, C.byref(c)), "kid_mts_fused_launches")
+        return c.value
+
     def profile(self, on=True):
         self._check(self.lib.kid_profile_enable(self.h, 1 if on else 0), "kid_profile_enable")
 

@@ -132,6 +132,8 @@ def load():
         lib.kid_hot_zero_mask.argtypes = [H, C.POINTER(C.c_uint64)]
     if hasattr(lib, "kid_cold_state"):   # a hook for tests (csrc/kid_rows.inc), not part of include/kid.h
         lib.kid_cold_state.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    if hasattr(lib, "kid_mts_fused_launches"):   # a hook for tests (csrc/kid_mts_host.inc), not part of include/kid.h
+        lib.kid_mts_fused_launches.argtypes = [H, C.POINTER(C.c_int64)]
     lib.kid_upload_bonds.argtypes = [H, C.POINTER(T.BondSoA)]
     lib.kid_download_bonds.argtypes = [H, C.POINTER(T.BondSoA)]
     lib.kid_evolve_icebergs_mts.argtypes = [H]

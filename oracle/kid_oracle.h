@@ -95,6 +95,8 @@ long ko_unpack_bergs(const ko_grid *g, const kid_params *p, kid_berg_soa *b, con
 /* multiple time stepping / DEM (oracle/kid_oracle_mts.c) */
 void ko_evolve_icebergs_mts(const ko_grid *g, const kid_params *p, kid_berg_soa *b, kid_bond_soa *bd, double *scalars);
 void ko_set_conglom_ids(const ko_grid *g, const kid_params *p, kid_berg_soa *b, kid_bond_soa *bd);
+/* calculate_force_dem for one pair given by value: id[2], x[26] in, out[40] (layouts at its definition) */
+void ko_dem_pair(const kid_params *p, int latlon, const int64_t *id, const double *x, double *out);
 void ko_orig_bond_length(const ko_grid *g, const kid_params *p, kid_berg_soa *b, kid_bond_soa *bd);
 double ko_quad_interp_depth(const ko_grid *g, const kid_params *p, double x, double y, int i, int j, double xi, double yj);
 void ko_run_step_mts(const ko_grid *g, const kid_params *p, kid_berg_soa *b, kid_bond_soa *bd, int first_visit,

@@ -439,6 +439,51 @@ static void calculate_force_dem(mts_ctx *c, int64_t k, int s, double dt, dem_sum
 #undef MIRROR_STATE
 }
 
+/* calculate_force_dem above for ONE pair given by value, on a context of two bergs with one bond each (tests/test_dem_pair_cpu.py
+ * holds it to a 50-digit restatement of IB:959-1242).  Berg 0 evaluates, berg 1 is its partner.
+ *   id[2];  x[KO_DEM_PAIR_NIN] = {fl_k, thickness, mass, length, width, lon_old, lat_old, uvel_old, vvel_old, ang_vel, rot} of berg 0,
+ *   the same eleven of berg 1, then tangd1, tangd2, rel_rotation of berg 0's side of the bond, and dt;
+ *   out[KO_DEM_PAIR_NOUT] = berg 0's bond {length, tangd1, tangd2, nstress, sstress, rel_rotation, F_x, F_y, Fd_x, Fd_y, T, T_d}
+ *   (the order of KID_BOND_*), the same twelve of berg 1's side, the sums the caller accumulates {F_x, F_y, T, Fd_x, Fd_y, T_d},
+ *   broken of the two sides, n_bonds of the two bergs (2 going in), error_count, nbonds_broken, bond_break_detected, and the derived
+ *   constant_area, constant_radius, dem_K_damp. */
+enum { KO_DEM_PAIR_NIN = 26, KO_DEM_PAIR_NOUT = 2 * KID_NBOND_F64 + 6 + 10 };
+void ko_dem_pair(const kid_params *p, int latlon, const int64_t *id, const double *x, double *out) {
+  static const int fld[11] = {KID_B_FL_K, KID_B_THICKNESS, KID_B_MASS, KID_B_LENGTH, KID_B_WIDTH, KID_B_LON_OLD, KID_B_LAT_OLD,
+                              KID_B_UVEL_OLD, KID_B_VVEL_OLD, KID_B_ANG_VEL, KID_B_ROT};
+  double bf[KID_NB_F64][2]; int32_t bi[KID_NB_I32][2]; int64_t ids[2] = {id[0], id[1]};
+  double df[KID_NBOND_F64][2]; int32_t count[2] = {1, 1}, broken[2] = {0, 0}; int64_t other_id[2] = {id[1], id[0]};
+  double scalars[KID_NSCALAR];
+  int64_t other_row[2] = {1, 0}; int32_t other_slot[2] = {0, 0}; unsigned char mark[2] = {0, 0};
+  memset(bf, 0, sizeof(bf)); memset(bi, 0, sizeof(bi)); memset(df, 0, sizeof(df)); memset(scalars, 0, sizeof(scalars));
+  kid_berg_soa b; kid_bond_soa bd; ko_grid g; mts_ctx c;
+  memset(&b, 0, sizeof(b)); memset(&bd, 0, sizeof(bd)); memset(&g, 0, sizeof(g)); memset(&c, 0, sizeof(c));
+  b.n = 2; b.id = ids;
+  for (int f = 0; f < KID_NB_F64; ++f) b.f64[f] = bf[f];
+  for (int f = 0; f < KID_NB_I32; ++f) b.i32[f] = bi[f];
+  for (int k = 0; k < 2; ++k) {
+    for (int q = 0; q < 11; ++q) bf[fld[q]][k] = x[11 * k + q];
+    bi[KID_BI_ALIVE][k] = 1; bi[KID_BI_N_BONDS][k] = 2;
+  }
+  bd.n = 2; bd.max_bonds = 1; bd.count = count; bd.other_id = other_id; bd.broken = broken;
+  for (int f = 0; f < KID_NBOND_F64; ++f) bd.f64[f] = df[f];
+  df[KID_BOND_TANGD1][0] = x[22]; df[KID_BOND_TANGD2][0] = x[23]; df[KID_BOND_REL_ROTATION][0] = x[24];
+  df[KID_BOND_TANGD1][1] = -x[22]; df[KID_BOND_TANGD2][1] = -x[23]; df[KID_BOND_REL_ROTATION][1] = -x[24];
+  g.d.grid_is_latlon = latlon ? 1 : 0;
+  c.g = &g; c.p = p; c.b = &b; c.bd = &bd; c.n = 2; c.mb = 1; c.scalars = scalars;
+  c.other_row = other_row; c.other_slot = other_slot; c.mark = mark;
+  derived_params(&c);
+  dem_sum D = {0., 0., 0., 0., 0., 0.};
+  calculate_force_dem(&c, 0, 0, x[25], &D);
+  int q = 0;
+  for (int k = 0; k < 2; ++k) for (int f = 0; f < KID_NBOND_F64; ++f) out[q++] = df[f][k];
+  out[q++] = D.F_x; out[q++] = D.F_y; out[q++] = D.T; out[q++] = D.Fd_x; out[q++] = D.Fd_y; out[q++] = D.T_d;
+  out[q++] = (double)broken[0]; out[q++] = (double)broken[1];
+  out[q++] = (double)bi[KID_BI_N_BONDS][0]; out[q++] = (double)bi[KID_BI_N_BONDS][1];
+  out[q++] = scalars[KID_S_ERROR_COUNT]; out[q++] = scalars[KID_S_NBONDS_BROKEN]; out[q++] = (double)c.bond_break_detected;
+  out[q++] = c.constant_area; out[q++] = c.constant_radius; out[q++] = c.dem_K_damp;
+}
+
 /* the speed limit block shared by accel_mts and accel_explicit_inner_mts (IB:1542-1563, 1918-1939) */
 static void speed_limit(const mts_ctx *c, int i, int j, double dt, double *uveln, double *vveln) {
   const kid_params *p = c->p; const ko_grid *g = c->g;

@@ -106,6 +106,8 @@ def load():
     lib.ko_unpack_bergs.argtypes = [C.POINTER(KoGrid), C.POINTER(T.Params), C.POINTER(T.BergSoA), C.POINTER(d), C.c_long]
     lib.ko_reference_order.restype = None
     lib.ko_reference_order.argtypes = [C.POINTER(T.BergSoA), C.POINTER(C.c_int64)]
+    lib.ko_dem_pair.restype = None   # calculate_force_dem for one pair by value: id[2], x[26] -> out[40] (kid_oracle_mts.c)
+    lib.ko_dem_pair.argtypes = [C.POINTER(T.Params), C.c_int, C.POINTER(C.c_int64), C.POINTER(d), C.POINTER(d)]
     return lib
 
 
