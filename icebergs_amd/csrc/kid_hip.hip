@@ -95,7 +95,6 @@ static int check_params(kid_handle *h, const kid_params *p) {
       h->err = "use_broken_bonds_for_substep_contact requires break_bonds_on_sub_steps, dem and iceberg_bonds_on (FW:1438-1447)"; return KID_EINVAL; }
     if (p->footloose) { h->err = "footloose together with mts is not implemented"; return KID_EUNSUPPORTED; }
   } else if (p->interactive_icebergs_on || p->iceberg_bonds_on) {
-    if (p->Runge_not_Verlet) { h->err = "interacting / bonded bergs under the single-time-step scheme are implemented for Verlet only (Runge_not_Verlet=F)"; return KID_EUNSUPPORTED; }
     // footloose children among interacting bergs: kid_fl_interact.inc.  With bonds a bonded edge element that would calve is the
     // reference's own FATAL (IB:2566-2569, 2585)
     if (p->footloose && p->iceberg_bonds_on) { h->err = "footloose together with iceberg_bonds_on: bonded footloose calving (edge elements that calve, IB:2566-2585) is not implemented"; return KID_EUNSUPPORTED; }

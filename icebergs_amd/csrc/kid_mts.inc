@@ -1501,7 +1501,12 @@ __global__ void __launch_bounds__(256) cell_conglom_kernel(const BergPtrs *__res
   m.cell_conglom[c] = id;
 }
 
-// ---- single-time-step scheme with interacting bergs (interactive_icebergs_on, mts=.false.), Verlet ------------------
+// ---- single-time-step scheme with interacting bergs (interactive_icebergs_on, mts=.false.), Verlet and RK4 ----------
+// Both integrators are two sweeps of one lane per berg (evolve_icebergs IB:7081-7200).  The first sweep reads of OTHER bergs only
+// what the second sweep writes (lon_old, lat_old, uvel_old, vvel_old), what no sweep writes (thickness, length, width, mass, id,
+// fl_k, conglom_id) and the cell tables of mts_prologue, so neither depends on the order of the rows:
+//   Verlet  sts_ia_velocity_kernel (velocities), sts_ia_position_kernel (update_verlet_position, the *_old copies)
+//   RK4     sts_ia_rk4_kernel (Runge_Kutta_stepping: four accel calls, position and velocity), sts_ia_rk4_old_kernel (the *_old copies)
 // accel IB:1950-2442 with the interactive terms
 __device__ __noinline__ void accel_sts_ia(const DevGrid &g, const kid_params &p, const BergPtrs &b, const MtsDev &m, long long k, const Env &e,
                                           int i, int j, double lat, double uvel, double vvel, double uvel0, double vvel0, double dt,
@@ -1667,6 +1672,105 @@ __global__ void __launch_bounds__(256) sts_ia_position_kernel(const DevGrid g, c
   if (err) unsafeAtomicAdd(m.red + MR_NERR, 1.);
   MF(KID_B_LON, k) = lonn; MF(KID_B_LAT, k) = latn; MI(KID_BI_INE, k) = i; MI(KID_BI_JNE, k) = j; MF(KID_B_XI, k) = xi; MF(KID_B_YJ, k) = yj;
   MF(KID_B_UVEL_OLD, k) = uvel1; MF(KID_B_VVEL_OLD, k) = vvel1; MF(KID_B_LON_OLD, k) = lonn; MF(KID_B_LAT_OLD, k) = latn;
+  if (i < g.isc || i > g.iec || j < g.jsc || j > g.jec) MI(KID_BI_ALIVE, k) = 0;
+}
+
+// first sweep of evolve_icebergs (IB:7106-7179) with Runge_Kutta_stepping (IB:7331-7683) and accel_sts_ia as its acceleration.
+// The four stages are one rolled body, as in the general build of rk4_step (kid_device.hpp), with the reference's own
+// arithmetic: the partial sums A = q1 (+ q4), B = q2 (+ q3) give (q1 + q4) + 2 (q2 + q3) of IB:7597-7616 in its association.
+// What a pair force reads of a berg -- *_old, the sizes, id, fl_k, conglom_id, the cell tables -- no lane writes here; what the
+// lane writes at its end is read by nobody else.  interactive_force centres its search on ine, jne of the ROW, the berg's cell
+// at the start of the step (the lists are not re-linked between stages): they are written after the last stage.
+__global__ void __launch_bounds__(256) sts_ia_rk4_kernel(const DevGrid g, const kid_params *__restrict__ pp, const BergPtrs *__restrict__ bt,
+                                                         const MtsDev *__restrict__ mt, const long long n) {
+  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
+  if (k >= n) return;
+  const BergPtrs &b = *bt; const kid_params &p = *pp; const MtsDev &m = *mt;
+  if (MI(KID_BI_ALIVE, k) == 0 || !(MF(KID_B_STATIC_BERG, k) < 0.5)) return;
+  if (MF(KID_B_HALO_BERG, k) >= 0.5) return;
+  const double dt = p.dt, dt_2 = 0.5 * dt, dt_6 = dt / 6.;
+  const int i1 = MI(KID_BI_INE, k), j1 = MI(KID_BI_JNE, k);
+  const double xi1 = MF(KID_B_XI, k), yj1 = MF(KID_B_YJ, k), lon1 = MF(KID_B_LON, k), lat1 = MF(KID_B_LAT, k);
+  const double uvel1 = MF(KID_B_UVEL, k), vvel1 = MF(KID_B_VVEL, k), axn0 = MF(KID_B_AXN, k), ayn0 = MF(KID_B_AYN, k);
+  const bool on_tang = (lat1 > 89.) && g.latlon;   // IB:7393
+  const double dydl = g.latlon ? (180. / p.pi) / p.Rearth : 1.;
+  Env e;
+  if (!p.old_interp_flds_order) {
+    e.uo = MF(KID_B_UO, k); e.vo = MF(KID_B_VO, k); e.ui = MF(KID_B_UI, k); e.vi = MF(KID_B_VI, k); e.ua = MF(KID_B_UA, k); e.va = MF(KID_B_VA, k);
+    e.ssh_x = MF(KID_B_SSH_X, k); e.ssh_y = MF(KID_B_SSH_Y, k); e.sst = MF(KID_B_SST, k); e.sss = MF(KID_B_SSS, k); e.cn = MF(KID_B_CN, k);
+    e.hi = MF(KID_B_HI, k); e.od = MF(KID_B_OD, k);
+  }
+  double bxn = 0., byn = 0.;
+  double x1 = 0., y1 = 0., xdot1 = 0., ydot1 = 0.;
+  if (on_tang) { rotpos_to_tang(p, lon1, lat1, x1, y1); rotvec_to_tang(p, lon1, uvel1, vvel1, xdot1, ydot1); }
+  double Au = 0., Bu = 0., Av = 0., Bv = 0., Aax = 0., Bax = 0., Aay = 0., Bay = 0., Aaxn = 0., Baxn = 0., Aayn = 0., Bayn = 0.;
+  double lon_s = lon1, lat_s = lat1, uvel_s = uvel1, vvel_s = vvel1, xdot_s = xdot1, ydot_s = ydot1;
+  int i = i1, j = j1, err = 0; double xi = xi1, yj = yj1;
+  bool bail = false;
+#pragma unroll 1
+  for (int s = 0; s < 4; ++s) {
+    if (s > 0) { i = i1; j = j1; xi = xi1; yj = yj1; adjust_index_and_ground<false>(g, p, nullptr, lon_s, lat_s, i, j, xi, yj, err, bail); }  // IB:7430-7431
+    const double dxdl = g.latlon ? (180. / p.pi) / (p.Rearth * cos((lat_s) * (p.pi / 180.))) : 1.;
+    double qu = uvel_s * dxdl, qv = vvel_s * dydl;
+    if (p.old_interp_flds_order) interp_flds(p, GlbCell{g, g.idx(i, j)}, xi, yj, e);
+    double axn_s = axn0, ayn_s = ayn0, ax, ay;
+    accel_sts_ia(g, p, b, m, k, e, i, j, lat_s, uvel_s, vvel_s, uvel1, vvel1, (s < 2) ? dt_2 : dt, ax, ay, axn_s, ayn_s, bxn, byn);
+    double qax = ax, qay = ay, qaxn = axn_s, qayn = ayn_s;
+    if (on_tang) {
+      qu = xdot_s; qv = ydot_s;
+      rotvec_to_tang(p, lon_s, ax, ay, qax, qay);
+      rotvec_to_tang(p, lon_s, axn_s, ayn_s, qaxn, qayn);
+    }
+    if (s == 0)      { Au = qu; Av = qv; Aax = qax; Aay = qay; Aaxn = qaxn; Aayn = qayn; }
+    else if (s == 1) { Bu = qu; Bv = qv; Bax = qax; Bay = qay; Baxn = qaxn; Bayn = qayn; }
+    else if (s == 2) { Bu = Bu + qu; Bv = Bv + qv; Bax = Bax + qax; Bay = Bay + qay; Baxn = Baxn + qaxn; Bayn = Bayn + qayn; }
+    else             { Au = Au + qu; Av = Av + qv; Aax = Aax + qax; Aay = Aay + qay; Aaxn = Aaxn + qaxn; Aayn = Aayn + qayn; }
+    if (s < 3) {  // X_{k+1} = X1 + c V_k ; V_{k+1} = V1 + c A_k   (c = dt/2, dt/2, dt)
+      const double c = (s < 2) ? dt_2 : dt;
+      if (on_tang) {
+        const double xs = x1 + c * qu, ys = y1 + c * qv;
+        xdot_s = xdot1 + c * qax; ydot_s = ydot1 + c * qay;
+        rotpos_from_tang(p, xs, ys, lon_s, lat_s);
+        rotvec_from_tang(p, lon_s, xdot_s, ydot_s, uvel_s, vvel_s);
+      } else {
+        lon_s = lon1 + c * qu; lat_s = lat1 + c * qv;
+        uvel_s = uvel1 + c * ax; vvel_s = vvel1 + c * ay;
+      }
+    }
+  }
+  double lonn, latn, uveln, vveln, axn, ayn;
+  if (on_tang) {
+    const double xn = x1 + dt_6 * (Au + 2. * Bu), yn = y1 + dt_6 * (Av + 2. * Bv);
+    const double xdotn = xdot1 + dt_6 * (Aax + 2. * Bax), ydotn = ydot1 + dt_6 * (Aay + 2. * Bay);
+    const double xddotn = (Aaxn + 2. * Baxn) / 6., yddotn = (Aayn + 2. * Bayn) / 6.;
+    rotpos_from_tang(p, xn, yn, lonn, latn);
+    rotvec_from_tang(p, lonn, xdotn, ydotn, uveln, vveln);
+    rotvec_from_tang(p, lonn, xddotn, yddotn, axn, ayn);   // bxn, byn stay as the 4th accel call left them
+  } else {
+    lonn = lon1 + dt_6 * (Au + 2. * Bu); latn = lat1 + dt_6 * (Av + 2. * Bv);
+    uveln = uvel1 + dt_6 * (Aax + 2. * Bax); vveln = vvel1 + dt_6 * (Aay + 2. * Bay);
+    axn = (Aaxn + 2. * Baxn) / 6.; ayn = (Aayn + 2. * Bayn) / 6.;
+    bxn = ((Aax + 2. * Bax) / 6) - (axn / 2); byn = ((Aay + 2. * Bay) / 6) - (ayn / 2);
+  }
+  i = i1; j = j1; xi = xi1; yj = yj1;
+  adjust_index_and_ground<false>(g, p, nullptr, lonn, latn, i, j, xi, yj, err, bail);
+  if (err) unsafeAtomicAdd(m.red + MR_NERR, 1.);
+  if (p.override_iceberg_velocities) { uveln = p.u_override; vveln = p.v_override; }   // IB:7151-7154
+  MF(KID_B_AXN, k) = axn; MF(KID_B_AYN, k) = ayn; MF(KID_B_BXN, k) = bxn; MF(KID_B_BYN, k) = byn;
+  MF(KID_B_UVEL, k) = uveln; MF(KID_B_VVEL, k) = vveln; MF(KID_B_LON, k) = lonn; MF(KID_B_LAT, k) = latn;
+  MF(KID_B_XI, k) = xi; MF(KID_B_YJ, k) = yj; MI(KID_BI_INE, k) = i; MI(KID_BI_JNE, k) = j;
+}
+// second sweep under RK4 (IB:7182-7197): nothing moves, the *_old members the next step's pair forces read take the new state
+__global__ void __launch_bounds__(256) sts_ia_rk4_old_kernel(const DevGrid g, const BergPtrs *__restrict__ bt, const long long n) {
+  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
+  if (k >= n) return;
+  const BergPtrs &b = *bt;
+  if (MI(KID_BI_ALIVE, k) == 0) return;
+  if (MF(KID_B_HALO_BERG, k) >= 0.5) { MI(KID_BI_ALIVE, k) = 0; MI(KID_BI_INE, k) = g.isc; MI(KID_BI_JNE, k) = g.jsc; return; }   // as sts_ia_position_kernel
+  if (!(MF(KID_B_STATIC_BERG, k) < 0.5)) return;
+  MF(KID_B_UVEL_OLD, k) = MF(KID_B_UVEL, k); MF(KID_B_VVEL_OLD, k) = MF(KID_B_VVEL, k);
+  MF(KID_B_LON_OLD, k) = MF(KID_B_LON, k); MF(KID_B_LAT_OLD, k) = MF(KID_B_LAT, k);
+  const int i = MI(KID_BI_INE, k), j = MI(KID_BI_JNE, k);
   if (i < g.isc || i > g.iec || j < g.jsc || j > g.jec) MI(KID_BI_ALIVE, k) = 0;
 }
 

@@ -503,10 +503,15 @@ int kid_evolve_icebergs_interactive(kid_handle *h) {
   h->zs.launched_other();   // (writes axn, ayn of any row)
   const long long n = h->n;
   const DevGrid g = dev_grid(h);
-  hipLaunchKernelGGL(sts_ia_velocity_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
-  hipLaunchKernelGGL(sts_ia_position_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
+  if (p.Runge_not_Verlet) {
+    hipLaunchKernelGGL(sts_ia_rk4_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
+    hipLaunchKernelGGL(sts_ia_rk4_old_kernel, MTS_GRID(n), g, (const BergPtrs *)h->d_bp, n);
+  } else {
+    hipLaunchKernelGGL(sts_ia_velocity_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
+    hipLaunchKernelGGL(sts_ia_position_kernel, MTS_GRID(n), g, (const kid_params *)h->d_params, (const BergPtrs *)h->d_bp, (const MtsDev *)h->d_mts, n);
+  }
   KID_HIP(h, hipGetLastError());
-  h->halo_rows_live = false;   // the position sweep has retired them
+  h->halo_rows_live = false;   // the second sweep has retired them
   return mts_fold_scalars(h);
 }
 // adjust_fl_berg_interactivity (IB:2765-2841, called at IB:5486): footloose children (fl_k = -1) out of everybody's contact

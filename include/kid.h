@@ -435,9 +435,10 @@ int kid_initialize_bonds(kid_handle *h, int32_t from_radii, double length, int64
  * reference's count, each bond from both its ends), *unmatched = those whose partner is not resident or holds no bond back to
  * this berg (what the reference's quality check flags).  A device reduction and one 16-byte read; either pointer may be NULL. */
 int kid_count_bonds(kid_handle *h, int64_t *nbonds, int64_t *unmatched);
-/* evolve_icebergs (IB:7081-7200) with interactive_icebergs_on under the single-time-step Verlet scheme: velocity sweep
- * with the spring/damping terms of interactive_force inside accel, then the position sweep (kid_evolve_icebergs
- * dispatches to it when interactive_icebergs_on and mts=F) */
+/* evolve_icebergs (IB:7081-7200) with interactive_icebergs_on under the single-time-step scheme, two sweeps with the
+ * spring/damping terms of interactive_force inside accel.  Verlet: the velocity sweep, then the position sweep.
+ * Runge_not_Verlet: the four stages of Runge_Kutta_stepping with position and velocity, then the *_old copies
+ * (kid_evolve_icebergs dispatches to it when interactive_icebergs_on and mts=F) */
 int kid_evolve_icebergs_interactive(kid_handle *h);
 
 /* ---- budgets: what a coupled host asks outside the step.  Device reductions over the resident state (csrc/kid_budget.inc)
