@@ -32,6 +32,7 @@
 #include "kid_rows_plan.hpp"
 #include "kid_fl_contact.hpp"
 #include "kid_reserve_plan.hpp"
+#include "kid_check_plan.hpp"
 
 using namespace kid;
 
@@ -563,3 +564,4 @@ int kid_profile_get(kid_handle *h, double *berg_ms, int64_t *launches, double *a
 #include "kid_halo.inc"
 #include "kid_chksum.inc"
 #include "kid_chksum_device.inc"
+#include "kid_check.inc"

@@ -126,6 +126,13 @@ class HipTile:
     def set_restart_locate(self, mode):
         self.ib.set_restart_locate(mode)
 
+    # the debug-mode invariants, per tile (halo copies may be resident)
+    def check_bergs(self, what="all"):
+        return self.ib.check_bergs(what)
+
+    def sorted_ids(self):
+        return self.ib.sorted_ids()
+
 
 class TileExchange:
     """ranks laid out as an ntx x nty array of tiles, rank = ty * ntx + tx (x fastest, like the reference's domain layout);
@@ -243,6 +250,31 @@ class TileExchange:
         self.sent += len(to_hi) + len(to_lo)
         self.received += len(from_lo) + len(from_hi)
         return from_lo, from_hi
+
+    def check_duplicates(self, tile):
+        """check_for_duplicates_in_parallel (FW:7344-7379) with the cross-PE half of check_for_duplicate_ids_in_list (FW:7424-7450):
+        every rank contributes `tile.sorted_ids()` (ascending int64, duplicates kept) -- the counts first, then the ids padded to the
+        longest list.  Returns (duplicates on a rank, summed over the ranks; ids that more than one rank owns), the same pair on every
+        rank.  Nothing is raised: the reference stops on either being non-zero, here the caller decides."""
+        dist = self.dist
+        ids = np.ascontiguousarray(np.asarray(tile.sorted_ids(), dtype=np.int64))
+        world = dist.get_world_size()
+        mine = torch.tensor([len(ids)], dtype=torch.int64, device=self.device)
+        counts = [torch.zeros(1, dtype=torch.int64, device=self.device) for _ in range(world)]
+        dist.all_gather(counts, mine)
+        counts = [int(c.item()) for c in counts]
+        longest = max(counts)
+        if longest == 0:      # FW:7358: no bergs anywhere
+            return 0, 0
+        padded = torch.zeros(longest, dtype=torch.int64, device=self.device)
+        padded[:len(ids)] = torch.from_numpy(ids).to(self.device)
+        lists = [torch.empty(longest, dtype=torch.int64, device=self.device) for _ in range(world)]
+        dist.all_gather(lists, padded)
+        per_rank = [t.cpu().numpy()[:c] for t, c in zip(lists, counts)]
+        on_a_rank = sum(int(np.count_nonzero(a[1:] == a[:-1])) for a in per_rank)    # FW:7418-7423
+        owners = np.concatenate([np.unique(a) for a in per_rank])                    # one entry per (rank, id)
+        _, seen = np.unique(owners, return_counts=True)
+        return on_a_rank, int(np.count_nonzero(seen > 1))                            # FW:7444: ii > 1
 
     def exchange(self, tile):
         """send_bergs_to_other_pes for this rank's tile: call it between evolve_icebergs and thermodynamics (IB:5447)"""

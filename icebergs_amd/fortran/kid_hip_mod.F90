@@ -47,6 +47,7 @@ module kid_hip_mod
   public :: kid_capacity, kid_reserve, kid_set_auto_reserve
   public :: kid_locate_bergs, kid_set_restart_locate
   public :: kid_grd_chksum, kid_bergs_chksum_device, kid_checksum_gridded, kid_chk_label, kid_chk_is_3d
+  public :: kid_check_report, kid_check_bergs, kid_sorted_ids
 
   interface
     integer(c_int) function kid_create(grid, params, capacity, device, handle) bind(C, name='kid_create')
@@ -149,6 +150,22 @@ module kid_hip_mod
       type(c_ptr), value :: h
       type(kid_grd_chksum), intent(out) :: recs(*)
       integer(c_int32_t), value :: n_out
+    end function
+    !> the debug-mode invariants on the resident rows (check_position FW:6576, count_out_of_order FW:4039, check_for_duplicates
+    !! FW:4118, duplicate ids FW:7418): what = a sum of KID_CHECK_POSITION, _ORDER, _DUPLICATES, _IDS (KID_CHECK_ALL); offenders are
+    !! counted in rep, never an error
+    integer(c_int) function kid_check_bergs(h, what, rep) bind(C, name='kid_check_bergs')
+      import :: c_int, c_ptr, c_int32_t, kid_check_report
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: what
+      type(kid_check_report), intent(out) :: rep
+    end function
+    !> the ids of the live rows on the computational domain, ascending; ids = c_loc of capacity integers, or c_null_ptr for n alone
+    integer(c_int) function kid_sorted_ids(h, ids, capacity, n) bind(C, name='kid_sorted_ids')
+      import :: c_int, c_ptr, c_int64_t
+      type(c_ptr), value :: h, ids
+      integer(c_int64_t), value :: capacity
+      integer(c_int64_t), intent(out) :: n
     end function
     integer(c_int) function kid_read_restart(h, dir) bind(C, name='kid_read_restart')
       import :: c_int, c_ptr, c_char

@@ -29,7 +29,7 @@ module kid_icebergs_glue
   public :: iceberg, bond, linked_list, kid_glue, inorder, insert_berg_into_list, kid_glue_init, kid_glue_set_calving, kid_glue_add_berg, kid_glue_count, &
             kid_glue_flatten, kid_glue_unflatten, kid_glue_clear_lists, kid_glue_end, kid_icebergs_run, kid_icebergs_init, kid_read_icebergs_nml, &
             kid_icebergs_init_bonds, kid_icebergs_run_local, kid_icebergs_run_finish, kid_exchange_sum, row_to_node, node_to_row, form_a_bond, kid_glue_find_berg, KID_CYCLIC_GLOBAL_DOMAIN, &
-            kid_icebergs_stock_pe, kid_icebergs_incr_mass, kid_glue_reserve, kid_glue_checksums
+            kid_icebergs_stock_pe, kid_icebergs_incr_mass, kid_glue_reserve, kid_glue_checksums, kid_glue_check_bergs
   !> FMS's mpp_domains flag for a zonally periodic global domain (mpp_parameter_mod), as DRV:44 passes it in dom_x_flags
   integer, parameter :: KID_CYCLIC_GLOBAL_DOMAIN = 2
 
@@ -1035,12 +1035,14 @@ contains
     fi%tau_is_velocity = merge(1, 0, bergs%tau_is_velocity) ; fi%cyclic_x = merge(1, 0, bergs%gd%Lx > 0.) ; fi%on_device = 0 ; fi%pad = 0
     call kid_check(kid_ingest_forcing(bergs%h, fi), bergs%h, 'kid_ingest_forcing')
     if (debug) call kid_glue_checksums(bergs, 'top of s/r run')                                ! IB:5385-5386
+    if (debug) call kid_glue_check_bergs(bergs, 'top of s/r run', position=.false.)
     ! calving source, IB:5203-5231, 5388, 5403
     if (bergs%calving_on) then
       ci%calving = c_loc(calving) ; ci%calving_hflx = c_loc(calving_hflx) ; ci%on_device = 0 ; ci%pad = 0
       call kid_check(kid_calving(bergs%h, ci, cscal), bergs%h, 'kid_calving')
     endif
     if (debug) call kid_glue_checksums(bergs, 's/r run after calving')                         ! IB:5404-5405
+    if (debug) call kid_glue_check_bergs(bergs, 's/r run after calving', position=.false.)
     ! the hot path, IB:5423-5512: this GPU's bergs
     call kid_check(kid_step_local(bergs%h), bergs%h, 'kid_step_local')
   end subroutine kid_icebergs_run_local
@@ -1065,6 +1067,7 @@ contains
     bergs%gcalv = 0. ; bergs%ghflx = 0.
     if (bergs%calving_on) call kid_check(kid_get_calving(bergs%h, c_loc(bergs%gcalv), c_loc(bergs%ghflx)), bergs%h, 'kid_get_calving')
     if (debug) call kid_glue_checksums(bergs, 'end of s/r run')   ! IB:5881-5882 (what follows writes the coupler's arrays only)
+    if (debug) call kid_glue_check_bergs(bergs, 'end of s/r run', position=.false.)
     if (bergs%passive_mode) return
     where (bergs%area(i0:i1, j0:j1) > 0.)
       calving(:,:) = bergs%gcalv(i0:i1, j0:j1) / bergs%area(i0:i1, j0:j1) + bergs%acc(i0:i1, j0:j1, KID_A_FLOATING_MELT+1)
@@ -1111,6 +1114,39 @@ contains
         'min', r%minv, 'max', r%maxv, 'mean', r%mean, 'rms', r%rms, 'sd', r%sd
     end subroutine print_record
   end subroutine kid_glue_checksums
+
+  !> The invariants the reference asserts under `debug` (kid_check_bergs on the resident rows): the two lines bergs_chksum prints
+  !! through count_out_of_order and check_for_duplicates, in the reference's formats (FW:4083-4084, 4154-4155), and the FATALs of
+  !! check_position (FW:6596, 6600) naming the smallest offending id.  '# out of order' is 0: rows have no list order, and every
+  !! traversal that depends on one sorts first.  The reference prints these lines inside bergs_chksum, right behind the
+  !! '# of bergs/cell' record; here they close the group, behind the checksum_gridded lines (kid_icebergs_run_local calls this
+  !! after kid_glue_checksums).  position = .false. leaves check_position out: the lines alone.  That is how kid_icebergs_run
+  !! calls it -- bergs_chksum does not call check_position either (the reference does that around evolve_icebergs, on xi, yj it
+  !! computed itself), and a host may hand over xi, yj that differ from pos_within_cell in the last bit, which is no reason to
+  !! stop a run.  A host that wants the assertion calls this routine itself.
+  subroutine kid_glue_check_bergs(g, label, position)
+    type(kid_glue), intent(inout) :: g
+    character(len=*), intent(in) :: label
+    logical, intent(in), optional :: position
+    type(kid_check_report) :: rep
+    integer(c_int32_t) :: what
+    what = int(KID_CHECK_ALL, c_int32_t)
+    if (present(position)) then
+      if (.not. position) what = int(KID_CHECK_ORDER + KID_CHECK_DUPLICATES + KID_CHECK_IDS, c_int32_t)
+    endif
+    call kid_check(kid_check_bergs(g%h, what, rep), g%h, 'kid_check_bergs')
+    write(*,'(a,3(x,a,i6),x,a)') 'KID, count_out_of_order:', '# out of order=', 0, '# in halo=', rep%n_in_halo, '# identicals=', rep%n_identical, label
+    write(*,'(a,2(x,a,i9),x,a)') 'KID, check_for_duplicates:', '# with same id=', rep%n_same_id, '# identical bergs=', rep%n_same_berg, label
+    if (rep%n_xiyj /= 0) then
+      write(0,'(3a,i0,a,i0,a,2(x,es12.4))') 'FATAL: KID, check_position, ', trim(label), ': berg has inconsistent xi,yj! id=', rep%first_id(1), &
+        ' (', rep%n_xiyj, ' bergs) largest differences', rep%max_dxi, rep%max_dyj
+      error stop 1
+    endif
+    if (rep%n_land /= 0) then
+      write(0,'(3a,i0,a,i0,a)') 'FATAL: KID, check_position, ', trim(label), ': berg is in a land cell! id=', rep%first_id(2), ' (', rep%n_land, ' bergs)'
+      error stop 1
+    endif
+  end subroutine kid_glue_check_bergs
 
   !> icebergs_stock_pe (IB:8102-8133) behind its argument list: index = KID_STOCK_WATER or KID_STOCK_HEAT (FMS's ISTOCK_WATER,
   !! ISTOCK_HEAT); any other index leaves value = 0., the reference's `case default`.  A device reduction over the resident bergs

@@ -572,6 +572,34 @@ class Icebergs:
                 lines.append(format_grd_chksum(name, rec, three_d=name in T.CHK_3D))
         return lines
 
+    # ---- the debug-mode invariants (check_position FW:6576, count_out_of_order FW:4039, check_for_duplicates FW:4118) ----
+    CHECKS = {"position": T.ENUMS["KID_CHECK_POSITION"], "order": T.ENUMS["KID_CHECK_ORDER"], "duplicates": T.ENUMS["KID_CHECK_DUPLICATES"],
+              "ids": T.ENUMS["KID_CHECK_IDS"], "all": T.ENUMS["KID_CHECK_ALL"]}
+
+    def check_bergs(self, what="all"):
+        """kid_check_bergs (include/kid.h) on the resident rows: the members of kid_check_report as a dict (first_id, first_row: lists
+        of four, for xiyj, land, same_id, dup_ids).  what: a name of CHECKS, several of them, or the mask itself.  Offenders are
+        reported, never raised."""
+        if isinstance(what, str):
+            what = (what,)
+        mask = int(what) if isinstance(what, (int, np.integer)) else sum(self.CHECKS[w] for w in set(what))
+        rep = T.CheckReport()
+        self._check(self.lib.kid_check_bergs(self.h, mask, C.byref(rep)), "kid_check_bergs")
+        out = {}
+        for name, ct in T.CheckReport._fields_:
+            v = getattr(rep, name)
+            out[name] = [int(x) for x in v] if hasattr(ct, "_length_") else (float(v) if ct is C.c_double else int(v))
+        return out
+
+    def sorted_ids(self):
+        """the ids of the live rows on the computational domain, ascending, duplicates kept (kid_sorted_ids): a numpy int64 array"""
+        n = C.c_int64()
+        self._check(self.lib.kid_sorted_ids(self.h, None, 0, C.byref(n)), "kid_sorted_ids")
+        ids = np.empty(int(n.value), dtype=np.int64)
+        if ids.size:
+            self._check(self.lib.kid_sorted_ids(self.h, ids.ctypes.data_as(C.POINTER(C.c_int64)), ids.size, C.byref(n)), "kid_sorted_ids")
+        return ids
+
     # ---- budgets (icebergs_stock_pe IB:8102-8133, icebergs_incr_mass IB:6046-6074, the budget block IB:5702-5727) ----
     def stock(self, index):
         """icebergs_stock_pe: index = types.ENUMS['KID_STOCK_WATER'] (kg) or ['KID_STOCK_HEAT'] (J); include/kid.h has the expression"""

@@ -25,7 +25,7 @@ SYMBOLS = [
     "kid_ingest_forcing", "kid_get_forcing",
     "kid_set_calving_params", "kid_set_calving_state", "kid_get_calving_state", "kid_calving", "kid_get_calving",
     "kid_restart_write_bergs", "kid_restart_count_bergs", "kid_restart_read_bergs", "kid_restart_write_bonds", "kid_restart_read_bonds", "kid_write_restart", "kid_read_restart", "kid_bergs_chksum",
-    "kid_bergs_chksum_device", "kid_checksum_gridded",
+    "kid_bergs_chksum_device", "kid_checksum_gridded", "kid_check_bergs", "kid_sorted_ids",
     "kid_locate_bergs", "kid_set_restart_locate",
     "kid_set_traj_params", "kid_record_posn", "kid_num_traj_records", "kid_write_trajectories",
     "kid_num_bond_traj_records", "kid_write_bond_trajectories",
@@ -118,7 +118,8 @@ def load():
     lib.kid_unpack_halo_fold.argtypes = [H, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
     lib.kid_fold_halo_self.argtypes = [H, C.c_int32, C.c_int32]
     lib.kid_read_restart.argtypes = [H, C.c_char_p]
-    older = ("kid_rebin_fused_count", "kid_hot_zero_mask", "kid_locate_bergs", "kid_set_restart_locate", "kid_bergs_chksum_device", "kid_checksum_gridded")   # absent from an older build loaded through KID_HIP_SO for an A/B run
+    older = ("kid_rebin_fused_count", "kid_hot_zero_mask", "kid_locate_bergs", "kid_set_restart_locate", "kid_bergs_chksum_device", "kid_checksum_gridded",
+             "kid_check_bergs", "kid_sorted_ids")   # absent from an older build loaded through KID_HIP_SO for an A/B run
     if hasattr(lib, "kid_locate_bergs"):
         lib.kid_locate_bergs.argtypes = [H, C.c_int, C.POINTER(C.c_int64)]
         lib.kid_set_restart_locate.argtypes = [H, C.c_int]
@@ -161,6 +162,9 @@ def load():
     if hasattr(lib, "kid_bergs_chksum_device"):
         lib.kid_bergs_chksum_device.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(T.GrdChksum)]
         lib.kid_checksum_gridded.argtypes = [H, C.POINTER(T.GrdChksum), C.c_int32]
+    if hasattr(lib, "kid_check_bergs"):
+        lib.kid_check_bergs.argtypes = [H, C.c_uint32, C.POINTER(T.CheckReport)]
+        lib.kid_sorted_ids.argtypes = [H, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     lib.kid_footloose_uniform.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32]
     lib.kid_set_footloose_step.argtypes = [H, C.c_int64]
     lib.kid_get_footloose_step.argtypes = [H, C.POINTER(C.c_int64)]

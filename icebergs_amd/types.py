@@ -104,6 +104,10 @@ class GrdChksum(C.Structure):
     _fields_ = _parse_struct(_src, "kid_grd_chksum", ENUMS)
 
 
+class CheckReport(C.Structure):
+    _fields_ = _parse_struct(_src, "kid_check_report", ENUMS)
+
+
 # checksum_gridded (FW:6694-6756): the label the reference prints for each record, in its order, and whether the field is 3-d
 CHK_LABELS = [
     "uo", "vo", "ua", "va", "ui", "vi", "ssh", "sst", "sss", "hi", "cn", "calving", "calving_hflx",

@@ -247,6 +247,28 @@ int kid_bergs_chksum_device(kid_handle *h, int64_t out[6], kid_grd_chksum *per_c
  * downloaded: two device sweeps over all fields, each a tree of fixed shape (no atomics), so two calls on the same state
  * return the same bits; the mean, rms and sd differ from the reference's serial sums by rounding. */
 int kid_checksum_gridded(kid_handle *h, kid_grd_chksum *out, int32_t n_out);
+/* ---- the invariants the reference asserts under debug = .true. (csrc/kid_check.inc), on the resident rows, nothing downloaded
+ * but the report.  `what` is a non-empty combination of
+ *   KID_CHECK_POSITION    check_position (FW:6576-6603) on every live row: n_rows, n_xiyj, n_land, max_dxi, max_dyj.  The
+ *                         recomputation is pos_within_cell as kid_locate_bergs, kid_read_restart and the immigrants' unpack
+ *                         store it, so a state they wrote has no mismatch.  A cell outside the data domain gives -999, -999:
+ *                         a mismatch, as in the reference; its mask is not read.
+ *   KID_CHECK_ORDER       count_out_of_order (FW:4039-4089): n_in_halo, n_identical.  "# out of order" has no counterpart:
+ *                         rows have no list order, and every traversal that depends on one sorts first.
+ *   KID_CHECK_DUPLICATES  check_for_duplicates (FW:4118-4158): n_same_id, n_same_berg (with the four *_fast members under mts).
+ *   KID_CHECK_IDS         check_for_duplicate_ids_in_list (FW:7405-7452) on this handle: n_dup_ids.
+ * The last three look at the live rows whose cell is on the computational domain: halo copies and leavers drop out, as they do
+ * from the reference's loops.  Equal means equal by value (Fortran's .ne.): a NaN equals nothing, -0.0 equals +0.0.  Members of
+ * the report that a check not asked for would fill are 0 (first_id, first_row: -1).  Offenders are reported, never an error:
+ * KID_OK when the checks ran.  KID_EINVAL: a NULL argument, `what` 0 or outside KID_CHECK_ALL, KID_CHECK_POSITION without a
+ * static grid.  Nothing is written to a row or added to KID_S_ERROR_COUNT; halo rows may be resident; deferred cold fields are
+ * gathered first, as for every reader.  Temporary device blocks sized by the number of rows, freed before return.  Cost: radix
+ * passes over the rows that count, plus m(m-1)/2 compares per group of m rows with equal start keys (none in a healthy state). */
+int kid_check_bergs(kid_handle *h, uint32_t what, kid_check_report *rep);
+/* the ids of the rows KID_CHECK_IDS counts, ascending, duplicates kept; *n = how many.  ids == NULL: the count only.  More than
+ * `capacity`: KID_ECAPACITY with *n set and nothing written.  What a decomposed run exchanges to find an id that two tiles own
+ * (check_for_duplicates_in_parallel, FW:7344-7403). */
+int kid_sorted_ids(kid_handle *h, int64_t *ids, int64_t capacity, int64_t *n);
 
 /* ---- trajectories: record_posn (FW:5328-5498) as a device pass that appends one record per selected berg
  * to buffers in HBM, and iceberg_trajectories.nc (icebergs_fms2io.F90:1631-2103) written from them: dimension "i", lon,

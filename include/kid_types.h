@@ -261,6 +261,23 @@ typedef struct kid_grd_chksum {
   int32_t present, pad_;
 } kid_grd_chksum;
 
+/* ---- the debug-mode invariants on the resident rows (kid_check_bergs, include/kid.h): which checks to run, and what they found.
+ * Offenders are counted, never an error.  The position check looks at every live row; the other three at the live rows whose
+ * cell is on the computational domain, the cells the reference's loops visit. ---- */
+enum { KID_CHECK_POSITION = 1, KID_CHECK_ORDER = 2, KID_CHECK_DUPLICATES = 4, KID_CHECK_IDS = 8, KID_CHECK_ALL = 15 };
+typedef struct kid_check_report {
+  int64_t n_rows;       /* live rows the position check looked at (halo copies included, as at FW:2115) */
+  int64_t n_xiyj;       /* check_position, FW:6592: stored xi or yj != pos_within_cell(lon, lat, ine, jne), IEEE '!=' (a NaN on either side counts) */
+  int64_t n_land;       /* check_position, FW:6598: msk(ine, jne) == 0 */
+  int64_t n_in_halo;    /* count_out_of_order's icnt2 (FW:4066-4079): live, halo_berg < 0.5, cell outside the computational domain */
+  int64_t n_identical;  /* count_out_of_order's icnt3 (FW:4057) on sorted lists: the sum of (m - 1) over groups of equal (cell, five start keys) */
+  int64_t n_same_id;    /* check_for_duplicates' icnt_id (FW:4141): pairs with sameid, the sum of m(m-1)/2 over groups of equal start keys */
+  int64_t n_same_berg;  /* check_for_duplicates' icnt_same (FW:4142): pairs with sameberg */
+  int64_t n_dup_ids;    /* check_for_duplicate_ids_in_list (FW:7418-7423) on this handle: the sum of (m - 1) over groups of equal id */
+  double  max_dxi, max_dyj;             /* largest |stored - recomputed| over rows where both are finite; 0 when none */
+  int64_t first_id[4], first_row[4];    /* smallest id among the offenders of xiyj, land, same_id, dup_ids and a row holding it; -1, -1 when none */
+} kid_check_report;
+
 /* diagnostics that the reference guards with `id_*>0` (diag_manager ids, FW:1567-1673) */
 enum {
   KID_DIAG_MELT_BY_CLASS  = 1 << 0,  /* IB:3119 */
