@@ -36,6 +36,8 @@ struct HipMem : kid::MemOwner<HipAllocator> {
 namespace {
 enum { KID_PERM_MAX = KID_NB_F64 + KID_NB_I32 + 2 };   // every field, the ids, the lane array of the slow-lane schedule
 struct PermTable { const void *src[KID_PERM_MAX]; void *dst[KID_PERM_MAX]; int n8, n4; };
+// one set of the slot-major bond tables (the members of MtsDev that are indexed by MB_S): argument of permute_bonds_kernel
+struct BondTables { int32_t *bcount = nullptr; int64_t *bother_id = nullptr; int32_t *bbroken = nullptr, *bother_row = nullptr, *bother_slot = nullptr; double *bf[KID_NBOND_F64] = {}; };
 }  // namespace
 
 // one set of what pack_forcing builds (kid_cells.inc): the per-cell records, the gathered cell packets of the hot build, and
@@ -133,6 +135,10 @@ struct kid_handle {
   // multiple time stepping / DEM
   MtsDev mts{}; MtsDev *d_mts = nullptr;
   int mb = 0; bool mts_ready = false, mts_dirty = true, have_bonds = false, visited = false;
+  // kid_set_bonds_follow_rows: compaction and re-binning accept a handle with bond tables and carry them along (bonds_move,
+  // kid_rows.inc).  bond_alt: the second set of tables, made at the first such permutation and dropped by kid_reserve; the two
+  // sets change places after every permutation.  bond_alt_rows: rows of it that may hold something else than what the tables are born with
+  bool bonds_follow = false; BondTables bond_alt{}; long long bond_alt_rows = 0;
   unsigned long long *d_key64[2] = {nullptr, nullptr}; int *d_rows[2] = {nullptr, nullptr};
   int *d_static_rows = nullptr; long long static_rows_n = -1, static_rows_cap = 0;   // rows ordered by the five static `inorder` keys (mts_build_order)
   unsigned long long *d_last_key = nullptr; int *d_order_flag = nullptr; long long order_n = -1;   // cell key of every row at the last sort: an unchanged population keeps its order
@@ -195,7 +201,7 @@ static int rebin_plan(kid_handle *h, bool dead_last);
 static int rebin_core(kid_handle *h, bool with_lane, int *list, const int *list_count), rebin_apply(kid_handle *h, bool with_lane, int *list, const int *list_count);
 static bool plain_namelist(const kid_handle *h), lanes_eligible(const kid_handle *h);   // kid_launch.inc
 static int repro_refuse(kid_handle *h);                                                  // kid_repro.inc
-static int mts_check_timeout(kid_handle *h), mts_fold_scalars(kid_handle *h);            // kid_mts_host.inc
+static int mts_check_timeout(kid_handle *h), mts_fold_scalars(kid_handle *h), mts_refresh(kid_handle *h);   // kid_mts_host.inc
 static int halo_bergs_supported(kid_handle *h, const char *what);                                                                           // kid_halo_bergs.inc
 static int auto_reserve(kid_handle *h, int64_t need, const char *what);                  // kid_reserve.inc
 }

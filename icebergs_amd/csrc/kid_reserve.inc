@@ -112,6 +112,10 @@ static int reserve_list(kid_handle *h, int64_t new_cap, ReserveList &L) {
   for (int32_t **q : {&h->cold.origin, &h->cold.origin_alt}) L.add(*q, RESERVE_LAZY);   // (the caller has materialised the cold fields: rows_enter)
   for (unsigned **q : {&h->d_key[0], &h->d_key[1], &h->d_idx[0], &h->d_idx[1], &h->d_cell_hist}) L.add(*q, RESERVE_LAZY);
   for (Scratch *t : {&h->sort_tmp, &h->scan_tmp, &h->cscan_tmp}) L.add(*t, RESERVE_LAZY);
+  // the second set of bond tables (bonds_move, kid_rows.inc): it holds nothing between two permutations, and the next one makes it at the new stride
+  L.add(h->bond_alt.bcount, RESERVE_LAZY); L.add(h->bond_alt.bother_id, RESERVE_LAZY); L.add(h->bond_alt.bbroken, RESERVE_LAZY);
+  L.add(h->bond_alt.bother_row, RESERVE_LAZY); L.add(h->bond_alt.bother_slot, RESERVE_LAZY);
+  for (auto &field : h->bond_alt.bf) L.add(field, RESERVE_LAZY);
   L.add(h->d_lane_alt, RESERVE_LAZY);
   L.add(h->d_keep, RESERVE_LAZY);
   L.add(h->d_static_rows, RESERVE_LAZY);   // a cached order, rebuilt from the rows (rows_orders_stale below)
@@ -134,6 +138,7 @@ static int reserve_core(kid_handle *h, int64_t new_cap) {
   if (had_orient) h->bp.orient = h->d_orient;
   h->rplan = kid_handle::RebinPlan{};
   h->static_rows_cap = 0;
+  h->bond_alt_rows = 0;
   rows_orders_stale(h);
   h->order_n = -1; h->labels_stale = true;
   if (h->sub_graph_exec) { (void)hipGraphExecDestroy(h->sub_graph_exec); h->sub_graph_exec = nullptr; h->sub_graph_n = -1; }

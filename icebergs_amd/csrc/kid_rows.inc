@@ -6,7 +6,8 @@
 //                  carries rp.srows_n through translate_rows_kernel
 //   rows_enter   : the prologue of an entry point that reads or changes rows
 //   permutation  : compaction and re-binning are both "build a permutation, gather every moving field into the second set of
-//                  arrays in one launch, swap" (perm_fields, rebin_apply, rebin_swap)
+//                  arrays in one launch, swap" (perm_fields, rebin_apply, rebin_swap); with kid_set_bonds_follow_rows the bond
+//                  tables go through the same permutation into a second set of tables (bonds_move, permute_bonds_kernel)
 // Textual unit of kid_hip.hip, included once.  The HIP-free decisions (skip rule, wire record) are kid_rows_plan.hpp.
 namespace {
 // one reservation per wave on *cursor: the lanes with `mine` get consecutive slots in lane order (all are counted, whether or
@@ -124,6 +125,50 @@ __global__ void __launch_bounds__(256) permute_all_kernel(const PermTable t, con
   }
   for (; f < t.n8; ++f) ((double *)t.dst[f])[k] = ((const double *)t.src[f])[p];
   for (; f < t.n8 + t.n4; ++f) ((int32_t *)t.dst[f])[k] = ((const int32_t *)t.src[f])[p];
+}
+// the inverse of a permutation that has none yet (KID_STABLE_RESORT: the comparison sort leaves only perm)
+__global__ void __launch_bounds__(256) invert_perm_kernel(const unsigned *perm, unsigned *inv, long long n) {
+  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
+  if (k < n) inv[perm[k]] = (unsigned)k;
+}
+// The bond tables through the permutation (kid_set_bonds_follow_rows): a thread owns destination row k < n_dst, reads its source
+// row p = perm[k] once and walks the list of p in list order, slot by slot; every store of a slot is to MB_S(s, k), so the
+// lanes of a wave store side by side in each of the sixteen planes, and the loads are the gather.  Partner references go
+// through kid::bond_ref_moved (kid_rows_plan.hpp) with keep / alive / inv, all indexed by source row (n_src of them).  Slots past
+// the list's end, the rows of a source that is not kept (the tail a re-binning leaves to be cut off) and the rows [n_dst, rows)
+// get the values the tables are born with: whatever is appended there later starts with no bonds.  src and dst share the stride.
+__global__ void __launch_bounds__(256) permute_bonds_kernel(const BondTables src, const BondTables dst, long long stride, int mb, const unsigned *perm,
+                                                            long long n_src, long long n_dst, long long rows, const int32_t *keep, const int32_t *alive, const unsigned *inv) {
+  const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
+  if (k >= rows) return;
+  long long p = 0;
+  int cnt = kid::BOND_FILL_COUNT;
+  if (k < n_dst) {
+    p = (long long)perm[k];
+    if (keep[p] != 0) cnt = min(max(src.bcount[p], 0), mb);
+  }
+  dst.bcount[k] = cnt;
+  for (int s = 0; s < mb; ++s) {
+    const size_t to = (size_t)s * (size_t)stride + (size_t)k;
+    if (s < cnt) {
+      const size_t from = (size_t)s * (size_t)stride + (size_t)p;
+      const int32_t o = src.bother_row[from];
+      const bool there = o >= 0 && (long long)o < n_src && keep[o] != 0;
+      const kid::BondRef r = kid::bond_ref_moved(o, src.bother_slot[from], there && alive[o] != 0, there ? (int32_t)inv[o] : -1);
+      double v[KID_NBOND_F64];
+#pragma unroll
+      for (int f = 0; f < KID_NBOND_F64; ++f) v[f] = src.bf[f][from];
+      dst.bother_id[to] = src.bother_id[from]; dst.bbroken[to] = src.bbroken[from];
+      dst.bother_row[to] = r.row; dst.bother_slot[to] = r.slot;
+#pragma unroll
+      for (int f = 0; f < KID_NBOND_F64; ++f) dst.bf[f][to] = v[f];
+    } else {
+      dst.bother_id[to] = (int64_t)kid::BOND_FILL_ID; dst.bbroken[to] = kid::BOND_FILL_BROKEN;
+      dst.bother_row[to] = kid::BOND_FILL_REF; dst.bother_slot[to] = kid::BOND_FILL_REF;
+#pragma unroll
+      for (int f = 0; f < KID_NBOND_F64; ++f) dst.bf[f][to] = kid::BOND_FILL_F64;
+    }
+  }
 }
 __global__ void __launch_bounds__(256) fill_i32_kernel(int32_t *p, int32_t v, long long n) {
   const long long k = (long long)blockIdx.x * 256ll + threadIdx.x;
@@ -275,7 +320,8 @@ int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive) {
 // The skip rule of a row permutation (kid_rows_plan.hpp) on this handle's switches and flags
 static bool field_never_written(const kid_handle *h, int f) {
   const kid_params &p = h->params;
-  return kid::field_never_written(NeverWrittenIn{p.footloose != 0, p.mts != 0, h->calving_on, p.periodic_reentry != 0, p.Runge_not_Verlet != 0,
+  // (the interacting evolve of the single-time-step scheme writes the *_old members and the rotation like the MTS path: same answer)
+  return kid::field_never_written(NeverWrittenIn{p.footloose != 0, p.mts != 0 || p.interactive_icebergs_on != 0, h->calving_on, p.periodic_reentry != 0, p.Runge_not_Verlet != 0,
                                                  h->flags.has_fl != 0, h->env_ever_stored}, f);
 }
 // The fp64 fields a launch enqueued now -- or a row permutation planned now -- may treat as zeros in every row, a bit per field
@@ -387,6 +433,45 @@ static int perm_fields(kid_handle *h, const unsigned *perm, long long n, bool de
   return KID_OK;
 }
 static const char *const bonds_keep_rows = "bergs with bonds keep their rows: no re-binning while bond tables exist";
+// The bond tables follow a planned permutation (kid_set_bonds_follow_rows), between its plan and rebin_apply: `alive` and `keep`
+// are still those of the source rows.  perm: the source row of each of the n_dst destination rows; inv: the new row of every
+// kept source row.  The second set of tables is made at the first call (as the primary set is born, at the handle's stride) and
+// the two change places afterwards; the device's table follows in mts_refresh, which the callers run once their rows have moved.
+// Nothing that is captured or held across steps points into either set: the sub-step graph and the cooperative launch take d_bp
+// and d_mts, the tables of pointers.
+static int bonds_move(kid_handle *h, const unsigned *perm, long long n_src, long long n_dst, const int32_t *keep, const unsigned *inv) {
+  if (!h->have_bonds || !h->mts_ready) return KID_OK;
+  MtsDev &m = h->mts;
+  BondTables &alt = h->bond_alt;
+  const int mb = h->mb > 0 ? h->mb : 1;
+  if (!alt.bcount) {
+    const size_t cap = (size_t)h->capacity, nb = (size_t)mb * cap;
+    KID_HIP(h, h->mem.dev(alt.bcount, cap, 0));
+    KID_HIP(h, h->mem.dev(alt.bother_id, nb, 0));
+    KID_HIP(h, h->mem.dev(alt.bbroken, nb, 0));
+    for (int32_t **q : {&alt.bother_row, &alt.bother_slot}) KID_HIP(h, h->mem.dev(*q, nb, 0xff));
+    for (auto &field : alt.bf) KID_HIP(h, h->mem.dev(field, nb, 0));
+    h->bond_alt_rows = 0;
+  }
+  BondTables src;
+  src.bcount = m.bcount; src.bother_id = m.bother_id; src.bbroken = m.bbroken; src.bother_row = m.bother_row; src.bother_slot = m.bother_slot;
+  for (int f = 0; f < KID_NBOND_F64; ++f) src.bf[f] = m.bf[f];
+  const long long rows = std::min<long long>(std::max(n_src, h->bond_alt_rows), h->capacity);
+  if (rows > 0) {   // (a compaction may keep no row: the rows that go are still put back to what they were born with)
+    hipLaunchKernelGGL(permute_bonds_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, (const BondTables)src, (const BondTables)alt, m.stride, mb,
+                       perm, n_src, n_dst, rows, keep, (const int32_t *)h->bp.i[KID_BI_ALIVE], inv);
+    KID_HIP(h, hipGetLastError());
+  }
+  m.bcount = alt.bcount; m.bother_id = alt.bother_id; m.bbroken = alt.bbroken; m.bother_row = alt.bother_row; m.bother_slot = alt.bother_slot;
+  for (int f = 0; f < KID_NBOND_F64; ++f) m.bf[f] = alt.bf[f];
+  alt = src;
+  h->bond_alt_rows = n_src;
+  h->mts_dirty = true;
+  // the bond-derived orientations are by row and are not moved: bond_orientations makes them again before the next spreading
+  // of a step; until then there are none, as after kid_upload_bergs
+  if (h->bp.orient) { h->bp.orient = nullptr; h->tables_dirty = true; }
+  return mts_refresh(h);   // d_mts names the new set before anything else is enqueued (the berg table follows in rebin_swap)
+}
 
 // Drop the rows that are not occupied and keep the order of the rest: the permutation "kept row k goes to the number of kept
 // rows before it", through the same one-launch gather and swap as a re-binning.  Every int32 field moves, `alive` included
@@ -395,7 +480,7 @@ int kid_compact_bergs(kid_handle *h) {
   if (!h) return KID_EINVAL;
   { const int rc = rows_enter(h, ROWS_CHANGE); if (rc) return rc; }
   if (h->n == 0) return KID_OK;
-  if (h->have_bonds) { h->err = bonds_keep_rows; return KID_EUNSUPPORTED; }   // the bond tables are indexed by row and nothing moves them
+  if (h->have_bonds && !h->bonds_follow) { h->err = bonds_keep_rows; return KID_EUNSUPPORTED; }   // the bond tables are indexed by row and move only when asked to (kid_set_bonds_follow_rows)
   { const int rc = perm_storage(h); if (rc) return rc; }
   const long long n = h->n;
   const unsigned nb = (unsigned)((n + 255) / 256);
@@ -411,6 +496,7 @@ int kid_compact_bergs(kid_handle *h) {
   { const int rc = count_rows(h, live, nullptr, &kept); if (rc) return rc; }
   rows_moved(h, false);
   { const int rc = perm_fields(h, perm, kept, false); if (rc) return rc; }
+  { const int rc = bonds_move(h, perm, n, kept, live, pos); if (rc) return rc; }   // pos: the new row of every kept row
   { const int rc = rebin_apply(h, false, nullptr, nullptr); if (rc) return rc; }
   rows_truncated(h, kept);
   return KID_OK;
@@ -431,7 +517,8 @@ int kid_compact_bergs(kid_handle *h) {
 // emigrants right after the re-binning.
 static bool rebin_fusable(const kid_handle *h) {
   const kid_params &p = h->params;
-  return !h->dbg.rebin_eager && !h->repro && !h->mig_mode && !h->pipelined && h->forc.have_forcing && p.Runge_not_Verlet && p.old_interp_flds_order &&
+  // (bond tables move with the copy, never later: a plain namelist with uploaded bonds is possible)
+  return !h->dbg.rebin_eager && !h->have_bonds && !h->repro && !h->mig_mode && !h->pipelined && h->forc.have_forcing && p.Runge_not_Verlet && p.old_interp_flds_order &&
          !p.static_icebergs && !p.mts && !p.interactive_icebergs_on && !p.footloose && !p.find_melt_using_spread_mass && !lanes_eligible(h) && plain_namelist(h);
 }
 int kid_move_berg_between_cells(kid_handle *h) {
@@ -442,12 +529,23 @@ int kid_move_berg_between_cells(kid_handle *h) {
   { const int rc_c = cold_settle(h); if (rc_c) return rc_c; }
   h->steps_since_sort = 0;
   if (h->n == 0) return KID_OK;
-  if (h->have_bonds) { h->err = bonds_keep_rows; return KID_EUNSUPPORTED; }
+  if (h->have_bonds && !h->bonds_follow) { h->err = bonds_keep_rows; return KID_EUNSUPPORTED; }
   // the dead sort to the tail; they are dropped the next time the host asks for the count (no synchronisation here)
   int rc = rebin_plan(h, true);
   if (rc) return rc;
   if (rebin_fusable(h)) h->rebin_pending = true;
-  else { rc = rebin_apply(h, false, nullptr, nullptr); if (rc) return rc; }
+  else {
+    if (h->have_bonds) {   // (never deferred: rebin_fusable says no)
+      const int32_t *live = nullptr;
+      rc = layout_flags(h, &live); if (rc) return rc;
+      if (h->stable_resort) {   // the comparison sort leaves no inverse; its input values, d_idx[0], are free now
+        hipLaunchKernelGGL(invert_perm_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->rplan.perm, h->d_idx[0], (long long)h->n);
+        KID_HIP(h, hipGetLastError());
+      }
+      rc = bonds_move(h, h->rplan.perm, h->n, h->n, live, h->d_idx[0]); if (rc) return rc;
+    }
+    rc = rebin_apply(h, false, nullptr, nullptr); if (rc) return rc;
+  }
   return KID_OK;
 }
 // the re-binning inside a step of the slow-lane schedule.  with_lane: the lane array moves with the rows and `list` (row
@@ -561,6 +659,34 @@ static bool rebin_table(const kid_handle *h, int K, RebinTab &tab) {
 int kid_set_resort_interval(kid_handle *h, int steps) {
   if (!h || steps < 0) return KID_EINVAL;
   h->resort_interval = steps;
+  return KID_OK;
+}
+// Bond tables follow their rows through kid_compact_bergs and kid_move_berg_between_cells (1) or pin them (0, the default)
+int kid_set_bonds_follow_rows(kid_handle *h, int on) {
+  if (!h) return KID_EINVAL;
+  if (on != 0 && on != 1) { h->err = "kid_set_bonds_follow_rows: on is 0 or 1"; return KID_EINVAL; }
+  h->bonds_follow = on == 1;
+  return KID_OK;
+}
+// bother_row and bother_slot as the kernels see them, in the layout of kid_bond_soa ([max_bonds * n], slot-major with stride n);
+// -1 past a list's end whatever the device holds there.  A hook for tests, like kid_cold_state.
+int kid_bond_partner_rows(kid_handle *h, int32_t *row, int32_t *slot, int64_t n) {
+  if (!h || !row || !slot) return KID_EINVAL;
+  if (!h->have_bonds || !h->mts_ready) { h->err = "no bonds were uploaded"; return KID_EINVAL; }
+  { const int rc = rows_enter(h, ROWS_READ, COLD_LEAVE); if (rc) return rc; }
+  if (n != h->n) { h->err = "kid_bond_partner_rows: n is not the handle's row count"; return KID_EINVAL; }
+  const size_t nn = (size_t)h->n, stride = (size_t)h->mts.stride;
+  if (nn == 0) return KID_OK;
+  std::vector<int32_t> count(nn);
+  KID_HIP(h, hipMemcpyAsync(count.data(), h->mts.bcount, nn * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  for (int s = 0; s < h->mb; ++s) {
+    KID_HIP(h, hipMemcpyAsync(row + (size_t)s * nn, h->mts.bother_row + (size_t)s * stride, nn * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    KID_HIP(h, hipMemcpyAsync(slot + (size_t)s * nn, h->mts.bother_slot + (size_t)s * stride, nn * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  }
+  KID_HIP(h, hipStreamSynchronize(h->stream));
+  for (int s = 0; s < h->mb; ++s)
+    for (size_t k = 0; k < nn; ++k)
+      if (s >= count[k]) row[(size_t)s * nn + k] = slot[(size_t)s * nn + k] = -1;
   return KID_OK;
 }
 // fp64 fields the last row permutation (compaction or re-binning) moved; the others were zeros that stayed where they were.

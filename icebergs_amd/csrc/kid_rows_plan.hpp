@@ -1,6 +1,7 @@
 // kid_rows_plan.hpp -- what the host decides about berg rows, as plain C++17: no HIP header, no handle.  The wire record of a
 // berg (kid_migrate.inc packs and decodes it, kid_halo_bergs.inc packs it) and the skip rule of the row permutation
-// (kid_rows.inc) are written down here once; tests/rows_plan_host.cpp enumerates both on the host.
+// (kid_rows.inc) are written down here once; tests/rows_plan_host.cpp enumerates both on the host.  So are the cold fields
+// (tests/cold_rows_host.cpp) and what a row permutation does to a bond's reference to its partner (tests/bond_rows_host.cpp).
 #pragma once
 #include "../../include/kid_types.h"
 
@@ -184,6 +185,43 @@ constexpr ColdSet cold_set(const ColdIn &s) {
 // instance do to it as one more 4-byte field.  Composing again never looks at cold data.
 constexpr void origin_compose(const int32_t *origin_src, const unsigned *perm, long long n, int32_t *origin_dst) {
   for (long long k = 0; k < n; ++k) origin_dst[k] = origin_src[perm[k]];
+}
+
+// Bond tables through a row permutation (kid_set_bonds_follow_rows; permute_bonds_kernel of kid_rows.inc).  The tables are
+// slot-major, x[s * stride + k], and a list is the slots s < count[k] of its row.  A list moves with its row, in list order.
+// What it holds of its partners is an id (kept as it is) and a reference, (row, slot) of the partner's end of the bond; the row
+// is a number of the OLD population, so it goes through the inverse permutation.  A partner that the permutation does not keep
+// -- a compaction drops it, a re-binning sorts it to the tail that the next count cuts off -- or that is dead leaves no row to
+// point at: the reference becomes (-1, -1), which is what kid_upload_bonds leaves for a partner it does not find among the live
+// rows; the slot stays in the list with its id, its fields and the list's count.
+// The values the tables are born with (mts_ensure): what a slot past a list's end holds, before and after.
+constexpr int32_t BOND_FILL_COUNT = 0, BOND_FILL_BROKEN = 0, BOND_FILL_REF = -1;   // (-1: the 0xff bytes of bother_row / bother_slot)
+constexpr long long BOND_FILL_ID = 0;
+constexpr double BOND_FILL_F64 = 0.;
+struct BondRef { int32_t row, slot; };
+// o, slot: the reference as the source list holds it.  partner_stays: row o is kept by the permutation and alive; inv_o: its new
+// row.  Neither is looked at when o < 0 (the caller need not look them up then)
+constexpr BondRef bond_ref_moved(int32_t o, int32_t slot, bool partner_stays, int32_t inv_o) {
+  return (o >= 0 && partner_stays) ? BondRef{inv_o, slot} : BondRef{BOND_FILL_REF, BOND_FILL_REF};
+}
+// the whole of it on the host, for the reference tables of a list (count, row, slot): destination row k < n_dst takes the list
+// of source row perm[k]; keep / alive / inv are indexed by source row (inv only where keep).  Strides may differ.
+constexpr void bond_refs_compose(const int32_t *count_src, const int32_t *row_src, const int32_t *slot_src, long long stride_src, const unsigned *perm,
+                                 long long n_dst, const int32_t *keep, const int32_t *alive, const int32_t *inv, int mb,
+                                 int32_t *count_dst, int32_t *row_dst, int32_t *slot_dst, long long stride_dst) {
+  for (long long k = 0; k < n_dst; ++k) {
+    const long long p = perm[k];
+    const int32_t cnt = keep[p] != 0 ? count_src[p] : BOND_FILL_COUNT;   // (a source row that is not kept: the tail a re-binning leaves to be cut off)
+    count_dst[k] = cnt;
+    for (int s = 0; s < mb; ++s) {
+      BondRef r{BOND_FILL_REF, BOND_FILL_REF};
+      if (s < cnt) {
+        const int32_t o = row_src[s * stride_src + p];
+        r = bond_ref_moved(o, slot_src[s * stride_src + p], o >= 0 && keep[o] != 0 && alive[o] != 0, o >= 0 && keep[o] != 0 ? inv[o] : -1);
+      }
+      row_dst[s * stride_dst + k] = r.row; slot_dst[s * stride_dst + k] = r.slot;
+    }
+  }
 }
 
 }  // namespace kid

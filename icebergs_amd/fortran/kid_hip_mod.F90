@@ -45,6 +45,7 @@ module kid_hip_mod
   public :: kid_calculate_mass_on_ocean, kid_halo_plane_count, kid_halo_buffer_count, kid_pack_halo_pair, kid_unpack_halo_pair
   public :: kid_unpack_halo_fold, kid_fold_halo_self
   public :: kid_capacity, kid_reserve, kid_set_auto_reserve
+  public :: kid_set_bonds_follow_rows, kid_bond_partner_rows
   public :: kid_locate_bergs, kid_set_restart_locate
   public :: kid_grd_chksum, kid_bergs_chksum_device, kid_checksum_gridded, kid_chk_label, kid_chk_is_3d
   public :: kid_check_report, kid_check_bergs, kid_sorted_ids
@@ -280,6 +281,19 @@ module kid_hip_mod
       import :: c_int, c_ptr
       type(c_ptr), value :: h
       integer(c_int), value :: steps
+    end function
+    ! bond tables follow their rows through kid_compact_bergs and kid_move_berg_between_cells (on = 1) or make both refuse (0)
+    integer(c_int) function kid_set_bonds_follow_rows(h, on) bind(C, name='kid_set_bonds_follow_rows')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+      integer(c_int), value :: on
+    end function
+    ! the partner rows and slots the kernels follow, (n, max_bonds) each in Fortran order; a hook for tests
+    integer(c_int) function kid_bond_partner_rows(h, row, slot, n) bind(C, name='kid_bond_partner_rows')
+      import :: c_int, c_ptr, c_int32_t, c_int64_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), intent(out) :: row(*), slot(*)
+      integer(c_int64_t), value :: n
     end function
     ! growable capacity: the rows a handle has room for, more of them, and growth ahead of the calls that append rows
     integer(c_int) function kid_capacity(h, rows) bind(C, name='kid_capacity')

@@ -490,6 +490,11 @@ class Icebergs:
     def upload_bonds(self, bonds):
         n, _ = self.num_bergs()
         self._check(self.lib.kid_upload_bonds(self.h, C.byref(self._bond_soa(bonds, n))), "kid_upload_bonds")
+        self._max_bonds = int(bonds["max_bonds"])
+
+    def _bond_slots(self):
+        """slots per berg of the handle's bond tables: those of the last upload_bonds, else the namelist's max_bonds (at least one)"""
+        return getattr(self, "_max_bonds", None) or max(1, int(self.params.max_bonds))
 
     def download_bonds(self, max_bonds):
         from .synthetic import empty_bonds
@@ -665,6 +670,21 @@ class Icebergs:
 
     def compact(self):
         self._check(self.lib.kid_compact_bergs(self.h), "kid_compact_bergs")
+
+    def set_bonds_follow_rows(self, on=True):
+        """bond tables follow their rows through compact() and move_berg_between_cells() (True) or make both refuse (False, the
+        default); kid_set_bonds_follow_rows in include/kid.h.  An int other than 0 or 1 is passed through and refused there."""
+        self._check(self.lib.kid_set_bonds_follow_rows(self.h, int(on)), "kid_set_bonds_follow_rows")
+
+    def bond_partner_rows(self):
+        """(rows, slots), each (max_bonds, n) int32: where the kernels find the other end of every bond, -1 past a list's end and
+        where no partner row is known (kid_bond_partner_rows, a hook for tests)"""
+        n, _ = self.num_bergs()
+        mb = self._bond_slots()
+        rows, slots = np.full((mb, n), -1, dtype=np.int32), np.full((mb, n), -1, dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.kid_bond_partner_rows(self.h, rows.ctypes.data_as(ip), slots.ctypes.data_as(ip), n), "kid_bond_partner_rows")
+        return rows, slots
 
     # ---- growable capacity (include/kid.h): host buffers are sized from num_bergs(), never from the capacity of __init__ ----
     @property

@@ -15,7 +15,7 @@ SO_PATH = os.environ.get("KID_HIP_SO", os.path.join(_CSRC, "libkid_hip.so"))  # 
 SYMBOLS = [
     "kid_create", "kid_destroy", "kid_memory_in_use", "kid_set_params", "kid_set_stream", "kid_sync", "kid_last_error", "kid_version",
     "kid_sizeof", "kid_set_static_grid", "kid_set_forcing", "kid_set_forcing_device", "kid_upload_bergs", "kid_download_bergs",
-    "kid_num_bergs", "kid_compact_bergs", "kid_move_berg_between_cells", "kid_set_resort_interval", "kid_capacity", "kid_reserve", "kid_set_auto_reserve", "kid_zero_accumulators", "kid_interp_gridded_fields_to_bergs",
+    "kid_num_bergs", "kid_compact_bergs", "kid_move_berg_between_cells", "kid_set_resort_interval", "kid_set_bonds_follow_rows", "kid_bond_partner_rows", "kid_capacity", "kid_reserve", "kid_set_auto_reserve", "kid_zero_accumulators", "kid_interp_gridded_fields_to_bergs",
     "kid_evolve_icebergs", "kid_footloose_calving", "kid_set_footloose_step", "kid_get_footloose_step", "kid_footloose_uniform", "kid_adjust_fl_berg_interactivity", "kid_thermodynamics", "kid_create_gridded_icebergs_fields",
     "kid_set_store_environment", "kid_set_reproducible_sums", "kid_set_iceberg_counter", "kid_get_iceberg_counter", "kid_step_local", "kid_step_gather", "kid_run_step", "kid_get_accumulators", "kid_accum_device_ptr", "kid_accum_live_count",
     "kid_bind_accum_buffer", "kid_bind_spread_mass_old", "kid_profile_enable", "kid_profile_get",
@@ -119,7 +119,7 @@ def load():
     lib.kid_fold_halo_self.argtypes = [H, C.c_int32, C.c_int32]
     lib.kid_read_restart.argtypes = [H, C.c_char_p]
     older = ("kid_rebin_fused_count", "kid_hot_zero_mask", "kid_locate_bergs", "kid_set_restart_locate", "kid_bergs_chksum_device", "kid_checksum_gridded",
-             "kid_check_bergs", "kid_sorted_ids")   # absent from an older build loaded through KID_HIP_SO for an A/B run
+             "kid_check_bergs", "kid_sorted_ids", "kid_set_bonds_follow_rows", "kid_bond_partner_rows")   # absent from an older build loaded through KID_HIP_SO for an A/B run
     if hasattr(lib, "kid_locate_bergs"):
         lib.kid_locate_bergs.argtypes = [H, C.c_int, C.POINTER(C.c_int64)]
         lib.kid_set_restart_locate.argtypes = [H, C.c_int]
@@ -148,6 +148,9 @@ def load():
     lib.kid_download_bergs.argtypes = [H, C.POINTER(T.BergSoA)]
     lib.kid_num_bergs.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.kid_set_resort_interval.argtypes = [H, C.c_int]
+    if hasattr(lib, "kid_set_bonds_follow_rows"):
+        lib.kid_set_bonds_follow_rows.argtypes = [H, C.c_int]
+        lib.kid_bond_partner_rows.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]
     lib.kid_capacity.argtypes = [H, C.POINTER(C.c_int64)]
     lib.kid_reserve.argtypes = [H, C.c_int64]
     lib.kid_set_auto_reserve.argtypes = [H, C.c_int64, C.c_double, C.c_int64]

@@ -94,12 +94,31 @@ int kid_num_bergs(kid_handle *h, int64_t *n_slots, int64_t *n_alive); /* slots i
 /* Drops melted / departed bergs and keeps the order of the rest.  One gather of every field into the second set of arrays that
  * the re-binning uses too: the first call of either allocates it (kid_memory_in_use then reports one more berg SoA for the
  * handle).  While bond tables exist (kid_upload_bonds, kid_initialize_bonds) rows keep their places: KID_EUNSUPPORTED, as from
- * kid_move_berg_between_cells, and nothing is changed. */
+ * kid_move_berg_between_cells, and nothing is changed -- unless kid_set_bonds_follow_rows has switched the tables to follow
+ * their rows: then the lists of the kept rows move with them, and a list that named a dropped row keeps the slot, its other_id
+ * and its count, with no partner row behind it. */
 int kid_compact_bergs(kid_handle *h);
 /* move_berg_between_cells (IB:5437): device counting sort of the SoA by cell (j-major), dead bergs dropped.  Results
- * never depend on it, speed does.  kid_run_step calls it every `steps` steps (default 16; 0 = never). */
+ * never depend on it, speed does.  kid_run_step calls it every `steps` steps (default 16; 0 = never; never with bond tables,
+ * mts or interacting bergs).  With bond tables: KID_EUNSUPPORTED and nothing changed, unless kid_set_bonds_follow_rows is on;
+ * then the tables are carried through the same permutation, at once (the copy is never left to the next step). */
 int kid_move_berg_between_cells(kid_handle *h);
 int kid_set_resort_interval(kid_handle *h, int steps);
+/* Bond tables follow their rows.  on = 0 (the default): kid_compact_bergs and kid_move_berg_between_cells refuse a handle with
+ * bond tables, as above.  on = 1: both accept it and carry the tables through their permutation in one more launch
+ * (csrc/kid_rows.inc, permute_bonds_kernel): every list moves with its row, in list order, with its other_id, broken marks and
+ * bond fields bit for bit, and the rows of the partners are re-derived through the inverse permutation.  A partner that is dead
+ * or dropped at that moment leaves the list's slot without a partner row, which is what kid_upload_bonds leaves for an id it
+ * does not find among the live rows; dead rows lose their own lists.  The first such call allocates a second set of tables
+ * (about 116 bytes per berg and slot; kid_memory_in_use reports it, kid_reserve frees it until the next permutation).  Any other
+ * value of `on` is KID_EINVAL.  Accepted at any time between steps, with or without bonds.  kid_run_step's own schedule is the
+ * same either way, and so is everything that refuses bonds for other reasons (kid_locate_bergs, tiles, halo rows,
+ * reproducible sums, footloose). */
+int kid_set_bonds_follow_rows(kid_handle *h, int on);
+/* A hook for tests: the partner rows and partner slots the kernels follow, as [max_bonds * n] each, slot-major with stride n
+ * (the layout of kid_bond_soa); -1 past a list's end and for a slot without a partner row.  n must be the handle's row count
+ * (KID_EINVAL otherwise, and when no bonds were uploaded). */
+int kid_bond_partner_rows(kid_handle *h, int32_t *row, int32_t *slot, int64_t n);
 
 /* ---- growable capacity: the one convenience of the reference's linked lists, which grow on the heap ---- */
 /* The handle's current row capacity: what kid_create was given, or what kid_reserve / auto-reserve have made of it since. */
